@@ -7,7 +7,7 @@ PostureTask + joint/velocity box limits, B = 65 536).  N > 1 (config 5): `--scal
 keeps 65 536 instances per GPU, `--scaling strong --global-batch 524288` splits BASELINE's batch
 over the ranks; instances are independent, so ranks never exchange data inside the timed region.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,16 +15,25 @@ The launcher only provides RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*: the proces
 TCP rendezvous (pink_amd.comm), the work is libpinkhip.so through ctypes, the gather of dq is
 ncclGather through the library's own RCCL binding.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run does only what the headline figure needs: set up, spin up + W warm-up steps, the K timed
+steps, the one JSON line (`ms_per_step` = wall milliseconds of one timed step).  `--dump-outputs DIR`
+then writes what the last timed step computed -- rank 0's dq, status, iters, path as DIR/<name>.npy
+(float64; a fixed seeded sample of the rows if they would exceed 64 MB) -- for output-for-output
+comparisons of two builds (the inputs are seeded: identical from run to run).  `--full` adds everything
+below (`--headline-only` / `--no-cpu-baseline` then drop parts of it again, as before).
+
+Rank 0 prints ONE JSON line.  Besides the contract fields it carries (from the timed steps themselves)
   roofline        HBM view of the fused kernel (algorithmic bytes / HIP-event time vs 8 TB/s)
   roofline_fp64   fp64-vector view of the same launches (flop model of SURVEY.md 8d from the measured
                   iteration counts vs 78.6 TFLOP/s): the fused kernel is VALU bound, not HBM bound
+and a `--full` run adds
   stack_only      the HBM-streaming kernel (build_ik's P, q)
   configs         BASELINE configs 2 (UR5, B = 4096) and 4 (JVRC + 2 barriers, B = 65 536)
   end_to_end      C-ABI call from host buffers (H2D + kernel + D2H), never `value`
   latency_B1_us   config 1 (UR5, batch of one): one solve_ik-sized call
   cpu_baseline    the oracle on the host cores: B0 per-call NumPy, B0' the reference's own build_ik
-                  (when /root/reference is mounted), B1 C single thread, B2 C all cores
+                  (when PINK_REFERENCE names a checkout of it), B1 C single thread, B2 C all cores
+  parity          every instance of rank 0's batch against the C oracle
 """
 from __future__ import annotations
 
@@ -160,11 +169,12 @@ def cpu_baseline(terms, budget_s: float = 20.0):
 
 
 def reference_build_ik_rate(terms):
-    """pink.build_ik verbatim (pink/solve_ik.py:152-203) on stub pinocchio/qpsolvers, per call -- only where
-    /root/reference is mounted (the build container); the GPU box has no reference checkout."""
-    ref_dir = os.environ.get("PINK_REFERENCE", "/root/reference")
-    if not os.path.isdir(os.path.join(ref_dir, "pink")):
-        return {"available": False, "reason": f"{ref_dir} not mounted on this host (measured in the build container: "
+    """pink.build_ik verbatim (pink/solve_ik.py:152-203) on stub pinocchio/qpsolvers, per call -- only where the
+    environment variable PINK_REFERENCE names a checkout of the reference (nothing outside the repository is read
+    otherwise); the GPU box has none."""
+    ref_dir = os.environ.get("PINK_REFERENCE")
+    if not ref_dir or not os.path.isdir(os.path.join(ref_dir, "pink")):
+        return {"available": False, "reason": "PINK_REFERENCE names no reference checkout on this host (measured where one was: "
                                               "profiles/cpu_baseline_container_r02.json)"}
     try:
         import importlib.util
@@ -785,6 +795,25 @@ def _keep_stdout_for_the_result() -> None:
         os.dup2(2, 1)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, res) -> None:
+    """What the timed path hands its caller (BatchResult: dq, status, iters, path) as out_dir/<name>.npy, float64.
+    Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the instances is written instead (`rows`: their indices)."""
+    arrays = {"dq": res.dq, "status": res.status, "iters": res.iters}
+    if res.path is not None:
+        arrays["path"] = res.path
+    B = res.dq.shape[0]
+    per_row = sum(8 * (a.size // max(B, 1)) for a in arrays.values())
+    if per_row * B > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(B, DUMP_LIMIT_BYTES // (per_row + 8), replace=False))
+        arrays = dict({k: a[rows] for k, a in arrays.items()}, rows=rows)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def _emit(text: str) -> None:
     data = (text + "\n").encode()
     if _RESULT_FD is None:
@@ -808,8 +837,13 @@ def main() -> None:
     ap.add_argument("--bounds", default="tight", choices=["tight", "kinematic"])
     ap.add_argument("--jacobians", default="dense", choices=["dense", "kinematic"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="only the timed headline (profiling runs)")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: only the timed headline (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="every figure besides the headline (configs, regimes, end-to-end, latency, "
+                                                        "closed loop, API level, CPU baseline, whole-batch parity)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure and nothing else
+        args.headline_only = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: this process becomes the launcher of N ranks (one per GPU) instead of silently running one
@@ -875,6 +909,8 @@ def main() -> None:
     elapsed = rdzv.allreduce_max(time.perf_counter() - t0)
 
     res = solver.download(dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     # what a host-fed job sees per rank: H2D + kernel + D2H through pinkhip_solve_host from pageable buffers, all ranks
     # at once (they share the host's PCIe / memory bandwidth: SURVEY.md 8(e) "report kernel-only and end-to-end")
     e2e_ranks = None

@@ -366,9 +366,8 @@ def test_floating_base_velocity_limit(backend):
 def test_urdf_reader_on_reference_robots():
     import os
 
-    path = "/root/reference/examples/robots/double_pendulum.urdf"
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not mounted")
+    # the reference's examples/robots/double_pendulum.urdf, stored as a data fixture
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "double_pendulum.urdf")
     m = pink_amd.load_urdf(path)
     assert m.nv == 2 and m.nq == 2
     cfg = Configuration(m, np.array([0.3, -0.4]))

@@ -9,6 +9,7 @@ import subprocess
 import sys
 import textwrap
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -118,7 +119,7 @@ def _strict_headline(stdout: str) -> dict:
 
 
 def test_two_rank_bench_control_flow(built, tmp_path):
-    head, line = _run(tmp_path, [])
+    head, line = _run(tmp_path, ["--full"])
     assert head["n_gpus"] == 2 and head["value"] == line["value"] and head["roofline"]["frac"] == line["roofline"]["frac"]
     assert set(head["cpu_baseline"]) >= {"value", "unit", "cores", "kind", "sample"} and head["cpu_baseline"]["kind"] == "port"
     assert head["parity"]["instances_compared"] == 6 and head["parity"]["max_abs_err"] < 1e-10 and head["parity"]["tolerance"] == 1e-8
@@ -139,6 +140,58 @@ def test_two_rank_bench_control_flow(built, tmp_path):
     for cfg in ("ur5_B4096", "jvrc_B65536"):
         c = line["configs"][cfg]
         assert c["failed"] == 0 and c["parity"]["max_abs_dq_err_vs_oracle"] < 1e-9 and c["stack_only"]["frac"] > 0
+
+
+def test_plain_run_is_the_headline_alone(built, tmp_path):
+    """Without --full the bench times the steps and prints the line: no CPU legs, parity, configs or other figures."""
+    head, line = _run(tmp_path, [], world=1)
+    assert head["n_gpus"] == 1 and head["steps"] == 2 and head["warmup"] == 1 and head["ms_per_step"] > 0 and head["value"] > 0
+    assert head["higher_is_better"] is True and line["solver_stats"]["failed"] == 0
+    for key in ("cpu_baseline", "parity", "stack_only", "other_regimes", "configs", "end_to_end", "latency_B1_us",
+                "closed_loop_on_device", "api_solve_ik_batch"):
+        assert key not in line, key
+    assert line["per_rank_end_to_end_ms"] is None
+
+
+def test_dump_outputs_writes_the_last_step(built, emu, tmp_path):
+    """--dump-outputs DIR: the arrays the timed path returned (dq, status, iters, path) as float64 .npy files, the same
+    from run to run, and what the solver computes for the seeded batch."""
+    from pink_amd import synthetic
+
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"out{k}"
+        (tmp_path / f"run{k}").mkdir()
+        _run(tmp_path / f"run{k}", ["--dump-outputs", str(out)], world=1)
+        dumps.append({n: np.load(out / f"{n}.npy") for n in ("dq", "status", "iters", "path")})
+        assert sorted(os.listdir(out)) == ["dq.npy", "iters.npy", "path.npy", "status.npy"]
+    terms = synthetic.make_terms("ur5", 6, bounds="tight", jacobians="dense", seed=synthetic.SEED0 + synthetic.CONFIGS["ur5"]["config_id"])
+    want = emu.solve(synthetic.pack(terms))
+    for d in dumps:
+        assert all(a.dtype == np.float64 for a in d.values())
+        assert d["dq"].shape == (6, 6) and np.array_equal(d["dq"], want.dq)
+        assert np.array_equal(d["status"], want.status) and np.array_equal(d["iters"], want.iters)
+        assert np.array_equal(d["path"], want.path)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
+def test_dump_outputs_samples_a_large_result(tmp_path, monkeypatch):
+    """Above the size limit a fixed seeded sample of the instances is written, with their indices."""
+    import bench
+    from pink_amd.batch_solver import BatchResult
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    B, nv = 1000, 30
+    rng = np.random.default_rng(3)
+    res = BatchResult(rng.normal(size=(B, nv)), np.zeros(B, np.int32), rng.integers(0, 9, B).astype(np.int32), np.ones(B, np.int8))
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / f"d{k}"), res)
+    got = {n: np.load(tmp_path / "d0" / f"{n}.npy") for n in ("dq", "status", "iters", "path", "rows")}
+    assert sum(a.nbytes for a in got.values()) <= 4096 and len(got["rows"]) > 0
+    rows = got["rows"].astype(np.int64)
+    assert np.array_equal(got["dq"], res.dq[rows]) and np.array_equal(got["iters"], res.iters[rows])
+    assert np.array_equal(np.load(tmp_path / "d1" / "rows.npy"), got["rows"])
 
 
 def test_two_rank_strong_scaling_splits_the_global_batch(built, tmp_path):
