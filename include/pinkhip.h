@@ -52,8 +52,9 @@ extern "C" {
  *   TABLEAU   sweep-tableau kernel, result certified by its KKT check (the common case)
  *   HANDOVER  the tableau's result failed the certificate (explicitly updated inverse, cond(H) >~ 1e8): solved again
  *             by the Goldfarb-Idnani code (Cholesky + orthogonal updates) inside the same launch
- *   ROUTED    sent to that code BEFORE the tableau iteration by the conditioning estimate max_i H_ii (H^-1)_ii > 1e10
- *             (a rank-deficient task stack made positive definite by `damping` alone, pink/solve_ik.py:55)
+ *   ROUTED    sent to that code BEFORE the tableau iteration by the conditioning estimate max_i H_ii (H^-1)_ii > 1e8
+ *             (PINKHIP_SWEEP_ROUTE_COND, a heuristic: weakly regularised stacks, e.g. made positive definite by `damping`
+ *             alone, pink/solve_ik.py:55; tests/test_conditioning_bands.py measures every path per decade of the estimate)
  *   GI        the Goldfarb-Idnani kernel by dispatch (shapes the tableau kernel does not serve, PINKHIP_SOLVER=packed) */
 #define PINKHIP_ITERS_COUNT(x) ((x) & 0xFFFFFF)
 #define PINKHIP_ITERS_PATH(x) (((x) >> 24) & 7)

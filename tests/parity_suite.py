@@ -242,12 +242,14 @@ def equality_edge_cases(solver):
     assert (bad.status == 2).all()
 
 
-def fuzz(solver, seeds, nv_lo=1, nv_hi=34, md_hi=5, ill=False, free_lead=0):
+def fuzz(solver, seeds, nv_lo=1, nv_hi=34, md_hi=5, ill=False, free_lead=0, exact_records=None):
     """Random mixes of box bounds (some missing, some with lb == ub), dense inequality rows (some
     duplicated), equalities, LM damping and dimensions; infeasible draws must be reported as such
     by both sides.  ``free_lead``: the first so many coordinates carry no bound and the draw has no rows (with 33 / 34
     coordinates: the instantiation that eliminates the leading coordinates, round 6) -- applied after every draw of the
-    seed, so that the seeds of the other shapes keep their problems."""
+    seed, so that the seeds of the other shapes keep their problems.  ``exact_records``: a list that receives, per feasible
+    instance, (seed, instance, kappa, |dq - x*|, |dq_oracle - x*|, |x*|, path) against the high-precision minimiser x*
+    (oracle/refined_kkt.py) -- the bar of the conditioning bands, beside the tolerance of this function."""
     n_checked = 0
     n_refuted0 = len(REFUTED)
     for sd in seeds:
@@ -257,6 +259,7 @@ def fuzz(solver, seeds, nv_lo=1, nv_hi=34, md_hi=5, ill=False, free_lead=0):
         neq = int(rng.integers(0, min(3, nv) + 1)) if rng.random() < 0.4 else 0
         mdi = int(rng.integers(0, md_hi)) if rng.random() < 0.5 else 0
         k = int(rng.integers(1, 7))
+        k_rows = k
         J = rng.normal(0, 0.5, size=(B, k, nv))
         e = 0.1 * rng.normal(size=(B, k))
         ep = rng.uniform(-0.5, 0.5, size=(B, nv))
@@ -329,6 +332,18 @@ def fuzz(solver, seeds, nv_lo=1, nv_hi=34, md_hi=5, ill=False, free_lead=0):
                 exact_anchor_check(J[b], e[b], ep[b], cost, dcost, lm, G[b], h[b], neq, out.dq[b], ref["dq"][b], tag=(sd, b))
                 CERTIFIED.append((sd, b, float(err[k]), float(cond[k])))
             n_checked += int(ok.sum())
+            if exact_records is not None:
+                from oracle.refined_kkt import batch_minimiser, conditioning_estimate
+
+                kk = np.nonzero(ok)[0]
+                pf = dict(J=np.concatenate([J, np.broadcast_to(eye, (B, nv, nv))], axis=1)[kk], e=np.concatenate([e, ep], axis=1)[kk],
+                          cost=np.concatenate([cost, np.full(nv, dcost)]), gain=np.ones(2), lm=np.array([lm, 0.0]), rows=[0, k_rows, k_rows + nv],
+                          damping=1e-12, G=G[kk], h=h[kk])
+                xe, _ = batch_minimiser(**pf, guesses=[ref["dq"][kk], out.dq[kk]], meq=neq)
+                kap = conditioning_estimate(ref["H"][kk])
+                for j, b in enumerate(kk):
+                    exact_records.append((sd, int(b), float(kap[j]), float(np.abs(out.dq[b] - xe[j]).max()), float(np.abs(ref["dq"][b] - xe[j]).max()),
+                                          float(np.abs(xe[j]).max()), int(out.path[b])))
     # The refuted verdicts of this call: listed (the GPU log shows them under -s / -rP) and BOUNDED -- the harness accepts
     # "the kernel returned the certified exact minimiser where the oracle's rule said inconsistent" as the rare round-off
     # event it is (one seed in 284 000 in round 5), not as a way for a kernel to pass by disagreeing with the oracle.
@@ -471,3 +486,275 @@ def small_stack_packing(solver):
                 Hr, cr = po.qp_objective(nv, [(J[b], e[b], cb, 0.8, 0.3), (np.eye(nv)[root:], ep[b], 0.2, 0.9, 0.1)], 1e-9)
                 assert np.abs(H[b] - Hr).max() <= 1e-13 * max(1.0, np.abs(Hr).max()), (nv, B, b)
                 assert np.abs(c[b] - cr).max() <= 1e-13 * max(1.0, np.abs(cr).max()), (nv, B, b)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Conditioning bands: every solver path against the high-precision minimiser (oracle/refined_kkt.py), binned by the host
+# estimate kappa = max_i H_ii (H^-1)_ii of the full stacked H.  For SPD H that bounds from above the estimate the tableau
+# kernel takes on any free set (guessed or final), i.e. the quantity it routes on (PINKHIP_SWEEP_ROUTE_COND).
+
+BANDS = [(1e2, 1e4), (1e4, 1e5), (1e5, 1e6), (1e6, 1e7), (1e7, 1e8), (1e8, 1e11)]
+BAND_NAMES = ["[1e2,1e4)", "[1e4,1e5)", "[1e5,1e6)", "[1e6,1e7)", "[1e7,1e8)", "[1e8,1e11)"]
+TOL_EXACT = 1e-8  # |dq - x*| <= TOL_EXACT max(1, |x*|) below ABS_BAR_COND, on every path
+# ... and from 1e6 on, alternatively not farther from x* than 10 x the fp64 C oracle, or than 10 cond eps |x*| (kappa for
+# cond).  Measured on the MI355X (2 000 draws per band and family): from [1e6, 1e7) on the fp64 oracle itself is 2e-8 ..
+# 5e-7 from x* and the Goldfarb-Idnani kernel (where handed-over and routed instances go) 1e-8 .. 8e-8: no fp64 solve
+# meets an absolute 1e-8 there on every draw, and the bands hold the kernels to the limits of fp64 instead
+ABS_BAR_COND = 1e6
+
+
+def banded_bar(kappa, xmax, err_oracle, floor=0.0):
+    """The bar of the conditioning bands for ``|dq - x*|``: ``TOL_EXACT max(1, |x*|)`` below ABS_BAR_COND; at and above it the
+    largest of that, ``10 |dq_oracle - x*|`` and ``10 kappa eps |x*|``, plus the reference's own accuracy ``floor max(1, |x*|)``
+    (its last refinement correction: at most 1e-7 relative, at kappa 1e10 and beyond)."""
+    kappa, xmax, err_oracle, floor = (np.asarray(v, float) for v in (kappa, xmax, err_oracle, floor))
+    scale = np.maximum(1.0, xmax)
+    fp64 = np.maximum(10.0 * err_oracle, 10.0 * kappa * np.finfo(float).eps * xmax)
+    return np.where(kappa < ABS_BAR_COND, TOL_EXACT * scale, np.maximum(TOL_EXACT * scale, fp64) + floor * scale)
+
+# family -> shapes: (nv, md of inequality rows, equalities, leading unbounded coordinates)
+BANDED_FAMILIES = {
+    "box": [(nv, 0, 0, 0) for nv in (8, 12, 16, 24, 30, 32, 40, 48, 50, 56, 64)],  # <NV,0,W>
+    "eliminating": [(33, 0, 0, 2), (34, 0, 0, 2), (34, 0, 0, 3)],  # <34,0,32>: nv 33 / 34 with n_free_lead >= 2
+    "dense": [(nv, md, 0, 0) for nv in (12, 24, 30, 34, 40, 50, 56) for md in (1, 2, 4, 6, 8)
+              if not (nv == 30 and md > 2) and not (nv == 12 and md > 4)] + [(50, 10, 0, 0), (50, 14, 0, 0)],  # <NV,MD,W>
+    "virtual": [(nv, md, 0, 0) for nv in (25, 28, 30, 32) for md in (3, 6, 8)] + [(nv, md, 0, 0) for nv in (12, 16) for md in (5, 8)],  # ik_sweepx.h
+    "equality": [(nv, md, neq, 0) for nv in (12, 24, 30) for md, neq in ((0, 1), (0, 3), (2, 1), (3, 2))],
+}
+
+
+def kappa_estimate(H):
+    from oracle.refined_kkt import conditioning_estimate
+
+    return conditioning_estimate(H)
+
+
+def band_of(kappa):
+    """Band index per instance (-1: below the control band or beyond the top one)."""
+    out = np.full(len(kappa), -1)
+    for i, (lo, hi) in enumerate(BANDS):
+        out[(kappa >= lo) & (kappa < hi)] = i
+    return out
+
+
+def _banded_draw(rng, nv, md, neq, lead, B):
+    """One batch of one shape: per instance a target log10 kappa uniform over the bands, placed by (a) a weak posture cost
+    (many flat directions) or (b) a dense task of k >= nv rows with planted log-spaced singular values and no posture task
+    (one flat direction); boxes loose (interior minimiser), tight (flat directions held by bounds) or with unbounded
+    coordinates (flat directions the solve itself must resolve)."""
+    mech = "a" if rng.random() < 0.5 else "b"
+    t = rng.uniform(2.0, 11.0, size=B)  # target log10 kappa
+    if mech == "a":
+        k = int(rng.integers(1, min(nv, 7) + 1)) if nv > 1 else 1
+        J = rng.normal(0, 0.5, size=(B, k, nv))
+        e = 0.1 * rng.normal(size=(B, k))
+        cost = rng.uniform(0.5, 2, size=(B, k))
+        col = (cost[..., None] ** 2 * J ** 2).sum(axis=1).max(axis=1)
+        dcost = np.sqrt(col / 10 ** t)  # H_ii ~ col, (H^-1)_ii ~ 1 / dcost^2 on the null space of J
+        lm = float(rng.choice([0.0, 1e-6]))
+        ep = rng.uniform(-0.5, 0.5, size=(B, nv))
+    else:
+        k = nv + int(rng.integers(0, 4))
+        U = np.linalg.qr(rng.normal(size=(B, k, nv)))[0]
+        V = np.linalg.qr(rng.normal(size=(B, nv, nv)))[0]
+        smin = 10 ** (-0.5 * (t - np.log10(nv)))
+        s = 10 ** (np.linspace(0.0, 1.0, nv)[None, :] * np.log10(np.minimum(smin, 1.0))[:, None])
+        J = np.einsum("bkn,bn,bmn->bkm", U, s, V)
+        y0 = rng.uniform(-0.5, 0.5, size=(B, nv))
+        e = -np.einsum("bkn,bn->bk", J, y0)  # W(-a e) = W J y0: the task's own minimiser is y0 (|x*| stays O(1))
+        cost = np.ones((B, k))
+        dcost, lm, ep = None, 0.0, None
+    kind = rng.integers(0, 3, size=B)  # 0 loose, 1 tight, 2 some coordinates unbounded
+    scale = np.where(kind == 0, rng.uniform(2.0, 5.0, size=B), 10 ** rng.uniform(-3, -1, size=B))[:, None]
+    lb = -rng.uniform(0.2, 1.0, size=(B, nv)) * scale
+    ub = rng.uniform(0.2, 1.0, size=(B, nv)) * scale
+    free = (kind[:, None] == 2) & (rng.random(size=(B, nv)) < rng.uniform(0.2, 0.7, size=(B, 1)))
+    lb[free] = -np.inf
+    ub[free & (rng.random(size=(B, nv)) < 0.7)] = np.inf
+    pinned = (kind[:, None] == 1) & (rng.random(size=(B, nv)) < 0.03)
+    lb[pinned] = ub[pinned] = 0.0
+    if lead:
+        lb[:, :lead], ub[:, :lead] = -np.inf, np.inf
+    A = rng.normal(size=(B, neq, nv))
+    bv = 0.01 * rng.normal(size=(B, neq))
+    Gi = rng.normal(size=(B, md, nv))
+    hi = rng.uniform(-0.01, 0.3, size=(B, md)) * np.minimum(scale, 1.0)
+    if md >= 2:
+        dup = rng.random(B) < 0.2
+        Gi[dup, 1], hi[dup, 1] = Gi[dup, 0], hi[dup, 0] + 0.01
+    tasks = [DenseTaskTerm(J=J, e=e, cost=cost, lm_damping=lm)]
+    Jp, ep_, cp, rows, lms = [J], [e], [cost], [0, k], [lm]
+    if mech == "a":
+        tasks.append(DiagonalTaskTerm(col0=0, e=ep, cost=np.repeat(dcost[:, None], nv, axis=1)))
+        Jp.append(np.broadcast_to(np.eye(nv), (B, nv, nv)))
+        ep_.append(ep)
+        cp.append(np.repeat(dcost[:, None], nv, axis=1))
+        rows.append(k + nv)
+        lms.append(0.0)
+    batch = pack_terms(nv, tasks, 0.005, 1e-12, boxes=[(lb, ub)], dense_rows=[(Gi, hi)] if md else (),
+                       equality_rows=[(A, bv)] if neq else (), batch_size=B)
+    eye = np.eye(nv)
+    hb = np.concatenate([ub, -lb], axis=1)
+    hb = np.where(np.isfinite(hb), hb, 1e30)
+    G = np.concatenate([A, np.broadcast_to(eye, (B, nv, nv)), np.broadcast_to(-eye, (B, nv, nv)), Gi], axis=1)
+    h = np.concatenate([bv, hb, hi], axis=1)
+    pf = dict(J=np.concatenate(Jp, axis=1), e=np.concatenate(ep_, axis=1), cost=np.concatenate(cp, axis=1), gain=np.ones(len(rows) - 1),
+              lm=np.array(lms), rows=np.array(rows, np.int32), damping=1e-12, G=np.ascontiguousarray(G), h=h, meq=neq)
+    return batch, pf, mech
+
+
+def banded_problems(family, per_band, seed0, batch=48, max_draws=4000):
+    """Rejection sampling into BANDS: draws of the family's shapes (round robin, seeded by seed0 + draw) until every band
+    holds ``per_band`` instances (or ``max_draws``).  Returns a list of (seed, shape, batch, pf, mech, keep, band) with ``keep``
+    the instances taken, and their band."""
+    shapes = BANDED_FAMILIES[family]
+    filled = np.zeros(len(BANDS), int)
+    out = []
+    for d in range(max_draws):
+        if (filled >= per_band).all():
+            break
+        sd = seed0 + d
+        shape, b, pf, mech = banded_draw(family, seed0, sd, batch)
+        H, _ = stacked_objective(pf)
+        band = band_of(kappa_estimate(H))
+        keep = []
+        for i in range(b.B):
+            if band[i] >= 0 and filled[band[i]] < per_band:
+                filled[band[i]] += 1
+                keep.append(i)
+        if keep:
+            keep = np.array(keep)
+            out.append((sd, shape, b, pf, mech, keep, band[keep]))
+    return out, filled
+
+
+def banded_draw(family, seed0, sd, batch=48):
+    """Draw ``sd`` of ``banded_problems(family, ..., seed0, batch)``: (shape, IKBatch, pink form, mechanism)."""
+    shapes = BANDED_FAMILIES[family]
+    shape = shapes[(sd - seed0) % len(shapes)]
+    return (shape,) + _banded_draw(np.random.default_rng(sd), *shape, batch)
+
+
+def stacked_objective(pf):
+    """fp64 H, c of a pink-form batch (the C oracle's stacking, no solve)."""
+    r = c_oracle.solve_ik_batch(**{k: v for k, v in pf.items()}, want_Hc=True, solve=False)
+    return r["H"], r["c"]
+
+
+def _take(pf, idx):
+    return {k: (v[idx] if k in ("J", "e", "G", "h") or (k == "cost" and np.ndim(v) == 2) else v) for k, v in pf.items()}
+
+
+def fuzz_banded(solver, family, per_band, seed0, problems=None, expect_paths=(0, 1, 2), reference=None):
+    """Solve the banded problems of ``family`` with ``solver`` and compare each feasible instance with the high-precision
+    minimiser x*.  Returns the per-instance record (dict of arrays: seed, instance, band, kappa, kappa_final (estimate on
+    the free coordinates at x*), path (``BatchResult.path``), status / oracle status, err (kernel) and err_oracle against x*, xmax = |x*|) and the
+    number of instances the reference handed to exact_minimiser.  Statuses must equal the oracle's (but for the REFUTED
+    rule of fuzz); every path reported must be in ``expect_paths``.  ``problems`` / ``reference``: reuse what an earlier
+    call drew / computed (the reference does not depend on the kernel)."""
+    from oracle.refined_kkt import batch_minimiser, conditioning_estimate
+
+    if problems is None:
+        problems, _ = banded_problems(family, per_band, seed0)
+    if reference is None:
+        reference = {}
+    rec = {k: [] for k in ("seed", "instance", "band", "kappa", "kappa_final", "path", "status", "status_oracle", "err", "err_oracle", "xmax", "floor")}
+    fallbacks = 0
+    for sd, shape, batch, pf, mech, keep, band in problems:
+        out = solver.solve(batch)
+        path = np.asarray(out.path)
+        assert np.isin(path[keep], expect_paths).all(), ("solver path outside", expect_paths, family, sd, shape, path[keep])
+        if sd not in reference:
+            ref = c_oracle.solve_ik_batch(**pf, want_Hc=True)
+            feas = np.nonzero(ref["status"][keep] == 0)[0]
+            kk = keep[feas]
+            xs = np.full((batch.B, batch.nv), np.nan)
+            kfin = np.full(batch.B, np.nan)
+            floor = np.zeros(batch.B)
+            if len(kk):
+                p = _take(pf, kk)
+                guess = [ref["dq"][kk]] + ([out.dq[kk]] if (out.status[kk] == 0).all() else [])
+                # (the reference's own accuracy: a tenth of the absolute bar below ABS_BAR_COND; above, where the bar is also
+                # 10 x the fp64 oracle's distance -- ~cond eps |x|, 1e-7 and more at the top -- up to 1e-7, and the bar of those
+                # instances is widened by it: banded_violations)
+                ftol = np.where(conditioning_estimate(ref["H"][kk]) < ABS_BAR_COND, 0.1 * TOL_EXACT, 10 * TOL_EXACT)
+                x, info = batch_minimiser(p["J"], p["e"], p["cost"], p["gain"], p["lm"], p["rows"], p["damping"], p["G"], p["h"], guess, meq=p["meq"],
+                                          floor_tol=ftol)
+                fallbacks += info["fallback"]
+                xs[kk] = x
+                floor[kk] = np.nan_to_num(info["floor"])
+                nv, neq = batch.nv, p["meq"]
+                at_bound = info["active"][:, neq:neq + 2 * nv].reshape(len(kk), 2, nv).any(axis=1)
+                kfin[kk] = conditioning_estimate(ref["H"][kk], ~at_bound)
+            reference[sd] = (ref, xs, kfin, conditioning_estimate(ref["H"]), floor)
+        ref, xs, kfin, kap, floor = reference[sd]
+        for j, i in enumerate(keep):
+            so, sk = int(ref["status"][i]), int(out.status[i])
+            if sk != so:
+                # the oracle's "inconsistent" refuted: only in that direction, only where the kernel's point is x* (below)
+                assert sk == 0 and so == 2, ("status differs from the oracle's", family, sd, int(i), sk, so, float(kap[i]))
+                REFUTED.append((sd, int(i)))
+                continue
+            rec["seed"].append(sd), rec["instance"].append(int(i)), rec["band"].append(int(band[j])), rec["kappa"].append(float(kap[i]))
+            rec["kappa_final"].append(float(kfin[i])), rec["floor"].append(float(floor[i])), rec["path"].append(int(path[i])), rec["status"].append(sk), rec["status_oracle"].append(so)
+            if so == 0:
+                xe = xs[i]
+                rec["err"].append(float(np.abs(out.dq[i] - xe).max())), rec["err_oracle"].append(float(np.abs(ref["dq"][i] - xe).max()))
+                rec["xmax"].append(float(np.abs(xe).max()))
+            else:
+                rec["err"].append(np.nan), rec["err_oracle"].append(np.nan), rec["xmax"].append(np.nan)
+    return {k: np.array(v) for k, v in rec.items()}, fallbacks
+
+
+def banded_violations(rec):
+    """Indices of the feasible instances beyond ``banded_bar``."""
+    ok = rec["status_oracle"] == 0
+    bar = banded_bar(rec["kappa"], rec["xmax"], rec["err_oracle"], rec["floor"])
+    return np.nonzero(ok & ~(rec["err"] <= bar))[0]
+
+
+def band_table(family, leg, rec):
+    """One line per band: count, worst |dq - x*| of the kernel and of the oracle, path shares."""
+    lines = []
+    names = ["tableau", "handover", "routed", "gi"]
+    for i, nm in enumerate(BAND_NAMES):
+        m = rec["band"] == i
+        f = m & (rec["status_oracle"] == 0)
+        n = int(m.sum())
+        sh = " ".join(f"{names[p]} {float((rec['path'][m] == p).mean()) if n else 0.0:.3f}" for p in range(4))
+        w = np.nonzero(f)[0]
+        w = int(w[np.nanargmax(rec["err"][w] / np.maximum(1.0, rec["xmax"][w]))]) if len(w) else None
+        at = f"  worst draw: seed {int(rec['seed'][w])} instance {int(rec['instance'][w])}" if w is not None else ""
+        lines.append(f"{family:11s} {leg:7s} {nm:11s} n={n:5d} feasible={int(f.sum()):5d} worst|dq-x*|={np.nanmax(rec['err'][f], initial=0.0):.2e} "
+                     f"oracle={np.nanmax(rec['err_oracle'][f], initial=0.0):.2e}  {sh}{at}")
+    return lines
+
+
+def ikbatch_form(batch):
+    """The reference's arguments (oracle/refined_kkt.batch_minimiser, c_oracle.solve_ik_batch) of a packed IKBatch: dense
+    tasks' rows, then each diagonal task as rows of the identity; G = [equalities, +I (ub), -I (-lb), dense rows] with
+    missing bounds as 1e30.  Safe-displacement terms of barriers (c_extra) are carried; barriers with a safe-displacement
+    gain are not (their diagonal term is formed by the kernel from barrier_safe_gain)."""
+    assert not (np.asarray(batch.barrier_safe_gain) > 0).any(), "barriers with a safe-displacement gain: not restated here"
+    B, nv = batch.B, batch.nv
+    rows = np.asarray(batch.task_rows)
+    J = np.zeros((B, int(rows[-1]), nv))
+    dense = 0
+    for t in range(len(rows) - 1):
+        r0, r1 = int(rows[t]), int(rows[t + 1])
+        if int(batch.task_kind[t]) == 0:
+            J[:, r0:r1] = batch.J[:, dense:dense + r1 - r0]
+            dense += r1 - r0
+        else:
+            c0 = int(batch.task_col0[t])
+            J[:, np.arange(r0, r1), c0 + np.arange(r1 - r0)] = 1.0
+    eye = np.broadcast_to(np.eye(nv), (B, nv, nv))
+    neq = int(batch.n_eq)
+    hb = np.concatenate([batch.ub, -batch.lb], axis=1)
+    G = np.concatenate([batch.Gd[:, :neq], eye, -eye, batch.Gd[:, neq:]], axis=1)
+    h = np.concatenate([batch.hd[:, :neq], np.where(np.isfinite(hb), hb, 1e30), batch.hd[:, neq:]], axis=1)
+    out = dict(J=J, e=np.asarray(batch.e), cost=np.asarray(batch.cost), gain=np.asarray(batch.gain), lm=np.asarray(batch.lm_damping),
+               rows=rows.astype(np.int32), damping=float(batch.damping), G=np.ascontiguousarray(G), h=np.ascontiguousarray(h), meq=neq)
+    if batch.c_extra is not None:
+        out["c_extra"] = np.asarray(batch.c_extra)
+    return out

@@ -234,7 +234,8 @@ def test_solver_path_is_reported_per_instance(backend, request, monkeypatch):
     good = pack_terms(nv, [DenseTaskTerm(J=J, e=e, cost=1.0), DiagonalTaskTerm(col0=0, e=0.1 * rng.normal(size=(B, nv)), cost=0.1)],
                       5e-3, 1e-12, boxes=box, batch_size=B)
     deficient = pack_terms(nv, [DenseTaskTerm(J=J, e=e, cost=1.0)], 5e-3, 1e-12, boxes=box, batch_size=B)
-    weak = pack_terms(nv, [DenseTaskTerm(J=J, e=e, cost=1.0), DiagonalTaskTerm(col0=0, e=0.1 * rng.normal(size=(B, nv)), cost=1e-7)],
+    ep_weak = 0.1 * rng.normal(size=(B, nv))
+    weak = pack_terms(nv, [DenseTaskTerm(J=J, e=e, cost=1.0), DiagonalTaskTerm(col0=0, e=ep_weak, cost=1e-7)],
                       5e-3, 1e-12, boxes=box, batch_size=B)
     r = s.solve(good)
     assert (r.status == 0).all() and (r.path == 0).all() and r.iters.max() < 100 and r.path_fractions()["tableau"] == 1.0
@@ -245,6 +246,14 @@ def test_solver_path_is_reported_per_instance(backend, request, monkeypatch):
     # free set -- so an instance whose ill-conditioned directions are held by bounds stays on the tableau, and the KKT
     # certificate decides; the packed run below is the check of the numbers either way)
     assert (rw.status == 0).all() and np.isin(rw.path, (0, 1, 2)).all() and rw.iters.max() < 200
+    # ... and whichever path took it, the point is the QP's minimiser to the contract's 1e-8 (oracle/refined_kkt.py: the KKT
+    # system of the active set refined in longdouble, P and q formed from the task rows)
+    from oracle.refined_kkt import batch_minimiser
+
+    eye = np.broadcast_to(np.eye(nv), (B, nv, nv))
+    xs, info = batch_minimiser(np.concatenate([J, eye], axis=1), np.concatenate([e, ep_weak], axis=1), np.r_[np.ones(6), np.full(nv, 1e-7)],
+                               [1.0, 1.0], [0.0, 0.0], [0, 6, 6 + nv], 1e-12, np.concatenate([eye, -eye], axis=1), np.full((B, 2 * nv), 0.05), [rw.dq])
+    assert np.abs(rw.dq - xs).max() <= 1e-8 * max(1.0, np.abs(xs).max()), (np.abs(rw.dq - xs).max(axis=1), rw.path)
     fr = rw.path_fractions()
     assert fr["goldfarb_idnani"] == 0.0 and abs(sum(fr.values()) - 1.0) < 1e-12
     monkeypatch.setenv("PINKHIP_SOLVER", "packed")
