@@ -368,6 +368,37 @@ typedef struct pinkhip_rollout_step {
 } pinkhip_rollout_step;
 int pinkhip_rollout_step_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_model *model,
                                 const pinkhip_rollout_step *args);
+
+/* ---- warm start of the tableau solvers from a caller-supplied active set (box-only problems, md == 0) ----
+ * An active set is a C-contiguous uint8 array active[B, nv], indexed by the stated tangent coordinate (also where the
+ * kernel eliminates leading coordinates, n_free_lead): 0 = free, 1 = fixed at lb, 2 = fixed at ub.
+ *
+ * active_in (may be NULL: the kernel's own start -- the diagonal guess in stack + solve, every coordinate free in the
+ * whole-step kernel) is a HINT and never trusted.  The kernel sanitises it per lane: any value other than 1 / 2, 1 with
+ * lb = -inf, 2 with ub = +inf and the eliminated leading coordinates are free.  Whatever the bytes hold the instance is
+ * solved to the same minimiser with the same status; a poor hint costs exchanges, nothing else.  It pays in a control
+ * loop: the joints saturated at step t are mostly those saturated at step t + 1, and an exact set costs no exchange.
+ *
+ * active_out (may be NULL) receives the set at the returned point: the tableau's final working set; for an instance
+ * another code solved (PINKHIP_PATH_HANDOVER / _ROUTED) the working set that code ended on; all zeros for
+ * status != 0, so that a failed step never seeds the next one.
+ *
+ * active_in == active_out is legal: every lane reads its byte before the iteration starts and the bytes of an instance
+ * are written by that instance's own lanes, after it.
+ *
+ * Both pointers are DEVICE pointers; the calls are enqueued on the handle's current compute stream and validate like
+ * their cold twins.  They return PINKHIP_E_UNSUPPORTED, having touched nothing, when md > 0, when the task stack is
+ * rank deficient by construction, when no warm instantiation fits the shape, or under PINKHIP_SOLVER=packed. */
+#define PINKHIP_HAS_WARM_START 1
+typedef struct pinkhip_warm {
+  const uint8_t *active_in; /* [B, nv] device, or NULL */
+  uint8_t *active_out;      /* [B, nv] device, or NULL */
+} pinkhip_warm;
+int pinkhip_solve_warm_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_problem *dev_in,
+                              const pinkhip_result *dev_out, const pinkhip_warm *warm);
+int pinkhip_rollout_step_warm_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_model *model,
+                                     const pinkhip_rollout_step *args, const pinkhip_warm *warm);
+
 /* q [B,nq], q_target [nq] or [B,nq] -> lb, ub [B,nv]; posture error written into e [B,K] at columns
  * e_off .. e_off + nv - root_nv (e may be NULL) */
 int pinkhip_limits_posture_device(pinkhip_handle *h, const pinkhip_model *model, int64_t B, double dt,

@@ -118,6 +118,12 @@ class RolloutStep(ctypes.Structure):
     ]
 
 
+class Warm(ctypes.Structure):
+    """``pinkhip_warm``: device addresses of the ``uint8 [B, nv]`` active sets (0 free, 1 at lb, 2 at ub), either may be NULL."""
+
+    _fields_ = [("active_in", ctypes.c_void_p), ("active_out", ctypes.c_void_p)]
+
+
 # every symbol include/pinkhip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "pinkhip_version", "pinkhip_device_count", "pinkhip_create", "pinkhip_destroy",
@@ -126,7 +132,7 @@ ABI_SYMBOLS = (
     "pinkhip_frame_task_strided_device", "pinkhip_model_create", "pinkhip_model_destroy", "pinkhip_fk_device",
     "pinkhip_fk_frame_tasks_device", "pinkhip_step_device", "pinkhip_rollout_step_device",
     "pinkhip_limits_posture_device", "pinkhip_check_limits_device", "pinkhip_integrate_device", "pinkhip_integrate_checked_device",
-    "pinkhip_pose_targets_device",
+    "pinkhip_pose_targets_device", "pinkhip_solve_warm_device", "pinkhip_rollout_step_warm_device",
     "pinkhip_comm_get_unique_id", "pinkhip_comm_init", "pinkhip_comm_gather", "pinkhip_comm_gather_bytes",
     "pinkhip_comm_allgather_bytes", "pinkhip_comm_destroy",
     "pinkhip_host_alloc", "pinkhip_host_free", "pinkhip_malloc", "pinkhip_free",
@@ -172,6 +178,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.pinkhip_fk_frame_tasks_device.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, vp, i64]
     lib.pinkhip_step_device.argtypes = [vp, vp, i64, ctypes.POINTER(Step)]
     lib.pinkhip_rollout_step_device.argtypes = [vp, ctypes.POINTER(Desc), vp, ctypes.POINTER(RolloutStep)]
+    lib.pinkhip_solve_warm_device.argtypes = [vp, ctypes.POINTER(Desc), ctypes.POINTER(Problem), ctypes.POINTER(Result), ctypes.POINTER(Warm)]
+    lib.pinkhip_rollout_step_warm_device.argtypes = [vp, ctypes.POINTER(Desc), vp, ctypes.POINTER(RolloutStep), ctypes.POINTER(Warm)]
     lib.pinkhip_limits_posture_device.argtypes = [vp, vp, i64, f64, f64, vp, vp, i32, vp, vp, vp, i32, i32]
     lib.pinkhip_check_limits_device.argtypes = [vp, vp, i64, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_int64)]
     lib.pinkhip_integrate_device.argtypes = [vp, vp, i64, vp, vp]

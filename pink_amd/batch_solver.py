@@ -15,7 +15,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import PackedArgs, PinkHipError, Problem, Result
+from ._lib import PackedArgs, PinkHipError, Problem, Result, Warm
 from .batch import IKBatch
 
 
@@ -39,6 +39,8 @@ class BatchResult:
     status: np.ndarray  # [B] int32, 0 = optimal (see include/pinkhip.h)
     iters: np.ndarray  # [B] int32 active-set iterations
     path: Optional[np.ndarray] = None  # [B] int8: which code solved the instance (index into PATH_NAMES)
+    # [B, nv] uint8: the active set at dq (0 free, 1 at lb, 2 at ub; all zero where status != 0) -- warm-start calls only
+    active: Optional[np.ndarray] = None
 
     @property
     def all_found(self) -> bool:
@@ -61,8 +63,9 @@ class BatchResult:
 class DeviceBatch:
     """A batch resident in HBM together with its output buffers."""
 
-    def __init__(self, solver: "BatchSolver", args: PackedArgs, out_ptrs=None):
+    def __init__(self, solver: "BatchSolver", args: PackedArgs, out_ptrs=None, warm: bool = False):
         self.solver = solver
+        self.d_active: Optional[int] = None
         self.args = args
         self.ptrs: Dict[str, int] = {}
         self.nbytes = 0
@@ -80,6 +83,10 @@ class DeviceBatch:
             self.d_iters = solver._malloc(max(4 * b.B, 8))
         else:
             self.d_dq, self.d_status, self.d_iters = (int(p) for p in out_ptrs)
+        if warm:
+            # the active set of the warm-start entry, read and written in place by every solve_device(): starts all free
+            self.d_active = solver._malloc(max(b.B * b.nv, 8))
+            solver._h2d(self.d_active, np.zeros(max(b.B * b.nv, 8), dtype=np.uint8))
         self.d_H: Optional[int] = None
         self.d_c: Optional[int] = None
         p = Problem()
@@ -93,11 +100,11 @@ class DeviceBatch:
     def free(self) -> None:
         s = self.solver
         outs = [self.d_dq, self.d_status, self.d_iters] if self.owns_outputs else []
-        for ptr in list(self.ptrs.values()) + outs + [self.d_H, self.d_c]:
+        for ptr in list(self.ptrs.values()) + outs + [self.d_H, self.d_c, self.d_active]:
             if ptr:
                 s._free(ptr)
         self.ptrs = {}
-        self.d_dq = self.d_status = self.d_iters = self.d_H = self.d_c = None
+        self.d_dq = self.d_status = self.d_iters = self.d_H = self.d_c = self.d_active = None
 
 
 class BatchSolver:
@@ -161,11 +168,35 @@ class BatchSolver:
         )
 
     # -- host-memory path ------------------------------------------------------
-    def solve(self, batch: IKBatch, max_iter: int = 0, out: Optional[BatchResult] = None) -> BatchResult:
+    def solve(self, batch: IKBatch, max_iter: int = 0, out: Optional[BatchResult] = None, *,
+              active_in: Optional[np.ndarray] = None, return_active: bool = False) -> BatchResult:
         """Stack and solve every instance of ``batch`` (host buffers in, host out).  ``out`` re-uses the result
-        arrays of an earlier call (e.g. page-locked ones from :meth:`pinned_result`)."""
-        a = PackedArgs(batch, max_iter)
+        arrays of an earlier call (e.g. page-locked ones from :meth:`pinned_result`).
+
+        ``active_in`` (``uint8 [B, nv]``: 0 free, 1 fixed at ``lb``, 2 fixed at ``ub`` -- typically ``BatchResult.active``
+        of the previous solve of a tracking loop) starts the tableau solver from that active set; it is a hint, the
+        minimiser does not depend on it.  With it or with ``return_active`` the call goes through upload, the
+        warm-start entry (``pinkhip_solve_warm_device``) and download, and the result carries ``active``.  Box-only
+        batches on the tableau kernels only: anything else raises :class:`PinkHipError` with code -5."""
         B, nv = batch.B, batch.nv
+        if active_in is not None or return_active:
+            if active_in is not None:
+                if not isinstance(active_in, np.ndarray) or active_in.dtype != np.uint8 or active_in.shape != (B, nv):
+                    raise ValueError(f"active_in must be a uint8 array of shape ({B}, {nv})")
+            if out is not None:
+                raise ValueError("out= is for the host-memory path: not together with active_in / return_active")
+            dev = self.upload(batch, max_iter, warm=True)
+            try:
+                if active_in is not None and B:
+                    self._h2d(dev.d_active, np.ascontiguousarray(active_in))
+                w = Warm()
+                w.active_in = dev.d_active if active_in is not None else None
+                w.active_out = dev.d_active
+                self.solve_warm_raw(dev.args.desc, dev.problem, dev.result, w)
+                return self.download(dev)
+            finally:
+                dev.free()
+        a = PackedArgs(batch, max_iter)
         if out is not None:
             dq, status, iters = out.dq, out.status, out.iters
             if dq.shape != (B, nv) or status.shape != (B,) or iters.shape != (B,):
@@ -267,13 +298,20 @@ class BatchSolver:
                                    Gd=mv(batch.Gd), hd=mv(batch.hd), c_extra=mv(batch.c_extra))
 
     # -- HBM-resident path -----------------------------------------------------
-    def upload(self, batch: IKBatch, max_iter: int = 0, out_ptrs=None) -> DeviceBatch:
+    def upload(self, batch: IKBatch, max_iter: int = 0, out_ptrs=None, warm: bool = False) -> DeviceBatch:
         """Copy a batch to HBM.  ``out_ptrs = (dq, status, iters)`` device addresses
-        makes the solve write into caller-owned buffers instead of library ones."""
-        return DeviceBatch(self, PackedArgs(batch, max_iter), out_ptrs)
+        makes the solve write into caller-owned buffers instead of library ones.  ``warm=True`` adds a device-resident
+        active set ``d_active`` (``uint8 [B, nv]``, zero-filled): ``solve_device`` then runs the warm-start entry on it in
+        place, for callers that refresh ``J / e / lb / ub`` on the device and solve again."""
+        return DeviceBatch(self, PackedArgs(batch, max_iter), out_ptrs, warm)
 
     def solve_device(self, dev: DeviceBatch) -> None:
         """Enqueue one stack+solve pass over a resident batch (asynchronous)."""
+        if dev.d_active is not None:
+            w = Warm()
+            w.active_in = w.active_out = dev.d_active
+            self.solve_warm_raw(dev.args.desc, dev.problem, dev.result, w)
+            return
         self._check(self._lib.pinkhip_solve_device(self._h, ctypes.byref(dev.args.desc), ctypes.byref(dev.problem), ctypes.byref(dev.result)))
 
     def stack_device(self, dev: DeviceBatch) -> None:
@@ -292,7 +330,12 @@ class BatchSolver:
             self._d2h(dq, dev.d_dq)
             self._d2h(status, dev.d_status)
             self._d2h(iters, dev.d_iters)
-        return BatchResult(dq, status, iters, split_iters(iters))
+        res = BatchResult(dq, status, iters, split_iters(iters))
+        if dev.d_active is not None:
+            res.active = np.zeros((b.B, b.nv), dtype=np.uint8)
+            if b.B and b.nv:
+                self._d2h(res.active, dev.d_active)
+        return res
 
     def download_stack(self, dev: DeviceBatch) -> Tuple[np.ndarray, np.ndarray]:
         b = dev.args.batch
@@ -408,6 +451,16 @@ class BatchSolver:
 
     def solve_raw(self, desc, problem, result) -> None:
         self._check(self._lib.pinkhip_solve_device(self._h, ctypes.byref(desc), ctypes.byref(problem), ctypes.byref(result)))
+
+    def solve_warm_raw(self, desc, problem, result, warm) -> None:
+        """``pinkhip_solve_warm_device``: ``warm`` is a :class:`pink_amd._lib.Warm` of device addresses."""
+        self._check(self._lib.pinkhip_solve_warm_device(self._h, ctypes.byref(desc), ctypes.byref(problem), ctypes.byref(result), ctypes.byref(warm)))
+
+    def rollout_step_warm(self, desc, model: int, args, warm) -> None:
+        """``pinkhip_rollout_step_warm_device``: the whole control step in one kernel, its tableau started from
+        ``warm.active_in``.  Raises where the cold call would return ``False``: a warm start was asked for explicitly."""
+        self._check(self._lib.pinkhip_rollout_step_warm_device(self._h, ctypes.byref(desc), ctypes.c_void_p(model), ctypes.byref(args),
+                                                               ctypes.byref(warm)))
 
     # -- RCCL gather of dq (one handle per GPU / process) ----------------------------
     def comm_unique_id(self) -> bytes:

@@ -29,8 +29,17 @@
 #endif
 #if PINKHIP_DEV_MD > 0
 #define PINKHIP_SWEEPX_TABLE(X) X(PINKHIP_DEV_NV, PINKHIP_DEV_MD, PINKHIP_DEV_W)
+#define PINKHIP_WSWEEP_TABLE(X)
+#define PINKHIP_WROLLOUT_TABLE(X)
 #else
 #define PINKHIP_SWEEPX_TABLE(X)
+// (the warm-start twins of the one box-only instantiation)
+#define PINKHIP_WSWEEP_TABLE(X) X(PINKHIP_DEV_NV, 0, PINKHIP_DEV_W)
+#if PINKHIP_DEV_NV > PINKHIP_DEV_W
+#define PINKHIP_WROLLOUT_TABLE(X) X(PINKHIP_DEV_NV, 64)
+#else
+#define PINKHIP_WROLLOUT_TABLE(X) X(PINKHIP_DEV_NV, PINKHIP_DEV_W)
+#endif
 #endif
 #else
 // X(NV, MD, W): the sweep-tableau kernel with VIRTUAL dense rows ik_solve_sweepx_kernel<NV, MD, W> (ik_sweepx.h): NV
@@ -50,6 +59,11 @@
 // ... and, with position-barrier rows formed on chip (X(NV, MD, W): NV + MD tableau rows on W lanes), for these
 // (NV + MD > W: virtual dense rows, ik_sweepx.h; listed ahead of the wider group that would also hold the robot)
 #define PINKHIP_ROLLOUT_DENSE_TABLE(X) X(12, 4, 16) X(30, 6, 32) X(30, 8, 64) X(34, 8, 64) X(50, 6, 64) X(50, 14, 64) X(56, 8, 64)
+// Warm-start twins (box-only, started from the caller's active set: ik_sweep.h WARM; tu_wsweep.hip / tu_wrollout.hip) of
+// the stack + solve kernel, X(NV, 0, W), and of the whole-step kernel, X(NV, W).  Sparse on purpose -- every entry is a
+// translation unit of minutes: a shape runs on the smallest entry that holds it.
+#define PINKHIP_WSWEEP_TABLE(X) X(16, 0, 16) X(30, 0, 32) X(34, 0, 32) X(50, 0, 64) X(64, 0, 64)
+#define PINKHIP_WROLLOUT_TABLE(X) X(16, 16) X(30, 32) X(50, 64) X(56, 64)
 #define PINKHIP_PACKED_TABLE(X)                                                                          \
   X(6, 8) X(8, 8) X(12, 16) X(16, 16) X(24, 32) X(30, 32) X(32, 32) X(34, 64) X(40, 64) X(48, 64) X(50, 64) X(56, 64) X(64, 64)
 #endif
@@ -82,6 +96,15 @@ inline SweepChoice select_sweep(int nv, int md, int n_free_lead = 0) {
 #define PINKHIP_PICK(NV_, MD_, W_) \
   if (nv <= NV_ && md <= MD_ && (md > 0) == (MD_ > 0) && (NV_ <= W_ || n_free_lead >= NV_ - W_)) return SweepChoice{NV_, MD_, W_};
   PINKHIP_SWEEP_TABLE(PINKHIP_PICK)
+#undef PINKHIP_PICK
+  return SweepChoice{0, 0, 0};
+}
+
+// Smallest warm-start instantiation of the stack + solve kernel that holds nv coordinates ({0, 0, 0}: none; box-only)
+inline SweepChoice select_sweep_warm(int nv, int n_free_lead = 0) {
+#define PINKHIP_PICK(NV_, MD_, W_) \
+  if (nv <= NV_ && (NV_ <= W_ || n_free_lead >= NV_ - W_)) return SweepChoice{NV_, MD_, W_};
+  PINKHIP_WSWEEP_TABLE(PINKHIP_PICK)
 #undef PINKHIP_PICK
   return SweepChoice{0, 0, 0};
 }
@@ -164,6 +187,16 @@ inline SweepChoice select_rollout_dense(int nv, int nj, int fk_doubles, int md, 
   PINKHIP_ROLLOUT_DENSE_TABLE(PINKHIP_PICK)
 #undef PINKHIP_PICK
   return SweepChoice{0, 0, 0};
+}
+
+// ... started from the caller's active set: the smallest entry of PINKHIP_WROLLOUT_TABLE that holds the robot and whose LDS
+// fits (explicitly asked for: no robot is sent back to the two-launch step)
+inline PackedChoice select_rollout_warm(int nv, int nj, int fk_doubles) {
+#define PINKHIP_PICK(NV_, W_) \
+  if (nv <= NV_ && nj <= W_ && 8 * rollout_lds_doubles(NV_, W_, fk_doubles) * (64 / W_) + 16 <= 65536) return PackedChoice{NV_, W_};
+  PINKHIP_WROLLOUT_TABLE(PINKHIP_PICK)
+#undef PINKHIP_PICK
+  return PackedChoice{0, 0};
 }
 
 inline PackedChoice select_rollout(int nv, int nj, int fk_doubles, bool needed = false) {

@@ -221,6 +221,11 @@ struct KernelArgs {
   int *status;
   int *iters;
   double *H_out, *c_out;  // stack-only kernel
+  // warm start (the *_warm kernels only; NULL everywhere else): active[B, nv] bytes, 0 = free, 1 = fixed at lb, 2 = fixed at
+  // ub (include/pinkhip.h, pinkhip_warm).  active_in is a hint the kernel sanitises, active_out the set at the returned point.
+  const uint8_t *active_in;
+  uint8_t *active_out;
 };
+
 
 }  // namespace pinkhip

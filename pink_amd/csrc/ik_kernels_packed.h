@@ -75,7 +75,9 @@ struct LdsP {
 // DENSE = false is the instantiation for problems without dense inequality / equality rows (box limits
 // only, md = 0): every dense-row branch and its state (row slacks, row norms, equality bookkeeping)
 // folds away at compile time.
-template <int NV, int W, bool DENSE = true, class Src = HbmTerms>
+// SET_OUT (the hand-over of the warm-start kernels, ik_sweep.h WARM): the working set the iteration ended on -- this code's
+// per-lane state of the box, 0 free / 1 at lb / 2 at ub -- goes to KernelArgs::active_out, zeros for a failed instance.
+template <int NV, int W, bool DENSE = true, class Src = HbmTerms, bool SET_OUT = false>
 __device__ __forceinline__ void ik_packed_instance(const KernelArgs &a, long long block, Src *terms = nullptr, bool only = true,
                                                    int path = PATH_GI) {
   // only: this lane's group is to be solved (the sweep-tableau kernel hands over the groups whose result did not pass
@@ -937,6 +939,10 @@ __device__ __forceinline__ void ik_packed_instance(const KernelArgs &a, long lon
     if (li == 0) {
       late->status[b] = status;
       if (late->iters) late->iters[b] = it | (path << kPathShift);
+    }
+    if constexpr (SET_OUT) {
+      uint8_t *const aout = late->active_out;
+      if (aout && in) aout[b * (long long)nv + li] = static_cast<uint8_t>(status == STATUS_OPTIMAL ? bstate : 0);
     }
   }
 }

@@ -175,8 +175,10 @@ struct FkTerms {
   }
 };
 
-template <int NV, int MD, int W>
+// WARM (box-only): the tableau starts from KernelArgs::active_in and leaves its final set in active_out (ik_sweep.h)
+template <int NV, int MD, int W, bool WARM = false>
 __device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long long block) {
+  static_assert(!WARM || MD == 0, "warm starts are box-only");
   constexpr int G = kWave / W;
   const ModelDev &m = a.fk.m;
   const int lane = lane_id();
@@ -254,7 +256,7 @@ __device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long l
     // (more tableau rows than lanes: the dense rows are virtual, ik_sweepx.h -- two robots per wavefront at nv = 30
     // with barrier rows instead of one)
     if constexpr (NV + MD > W) st_sweep = ik_sweepx_instance<NV, MD, W, FkTerms<W>>(a.k, block, &t);
-    else st_sweep = ik_sweep_instance<NV, MD, W, FkTerms<W>>(a.k, block, &t);
+    else st_sweep = ik_sweep_instance<NV, MD, W, FkTerms<W>, WARM>(a.k, block, &t);
   }
   // a result that fails its KKT certificate is not integrated: the Goldfarb-Idnani code solves that robot's QP again
   // (ik_sweep.h, ik_solve_sweep_body).  It forms the rows from the kinematics like the tableau did, and the tableau's
@@ -273,7 +275,8 @@ __device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long l
     wave_sync();
     keep_frame_positions(*again);
     const_row_errors(*again, t2);
-    ik_packed_instance<NV, W, (MD > 0), FkTerms<W>>(again->k, block, &t2, over,
+    // (WARM: it leaves the working set it ends on in active_out)
+    ik_packed_instance<NV, W, (MD > 0), FkTerms<W>, WARM>(again->k, block, &t2, over,
                                                      again->k.rank_deficient ? PATH_GI : (st_sweep == STATUS_ROUTED ? PATH_ROUTED : PATH_HANDOVER));
     if (over) t.x = t2.x, t.status = t2.status;
   }
@@ -307,6 +310,12 @@ __device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long l
 template <int NV, int MD, int W>
 __global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_ROLLOUT(NV + MD) ik_rollout_kernel(RolloutArgs a) {
   ik_rollout_instance<NV, MD, W>(a, block_id());
+}
+
+// ... whose tableau starts from the caller's active set (tu_wrollout.hip, PINKHIP_WROLLOUT_TABLE): the budget of the cold twin
+template <int NV, int W>
+__global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_ROLLOUT(NV) ik_rollout_warm_kernel(RolloutArgs a) {
+  ik_rollout_instance<NV, 0, W, true>(a, block_id());
 }
 
 }  // namespace pinkhip

@@ -150,7 +150,15 @@ struct SweepLds {
 // wavefront on 32-lane groups instead of one on 64 lanes.  An instance whose leading coordinates DO carry a bound (the
 // host side only picks this instantiation when the caller says they do not: pinkhip_desc::n_free_lead) goes to the
 // Goldfarb-Idnani kernel.
-template <int NVT, int MD, int W, class Src = HbmTerms>
+//
+// WARM (box-only, the *_warm kernels): the start is the caller's active set, KernelArgs::active_in -- one byte per stated
+// coordinate, 0 free, 1 fixed at lb, 2 fixed at ub -- where the pointer is not NULL, and the set at the returned point goes
+// to KernelArgs::active_out.  The bytes are a hint that is never trusted: anything but 1 / 2, a bound that is infinite,
+// padding lanes and eliminated front coordinates are free; single principal pivoting needs nothing of its starting basis, so
+// a wrong hint costs the exchanges that repair it and nothing else -- Murty's rule, the iteration cap, the conditioning
+// estimate, the certificate and the hand-over are what they are without it.  Every lane reads its byte here, before the
+// iteration; the bytes of an instance are written at its write-out, by its own group: active_in == active_out is legal.
+template <int NVT, int MD, int W, class Src = HbmTerms, bool WARM = false>
 __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long block, Src *terms = nullptr) {
   constexpr int NE = NVT > W ? NVT - W : 0;  // eliminated front coordinates
   constexpr int NV = NVT - NE;               // coordinates of the tableau
@@ -161,6 +169,7 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   constexpr bool PPM = !DENSE && PINKHIP_SWEEP_PPM;                                  // box-only: the whole iteration
   constexpr bool PPMD = DENSE && PINKHIP_SWEEP_PPM && PINKHIP_SWEEP_PPM_DENSE && (!Src::kOnTheFly || PINKHIP_ROLLOUT_PPM_DENSE);  // dense rows: in front of the dual method
   constexpr bool PPX = PPM || PPMD;
+  static_assert(!WARM || PPM, "a warm start is a start of the principal pivoting of the box-only instantiations");
   constexpr int G = kWave / W;
   constexpr double INF = INFINITY;
   constexpr double BIG = 1e300;
@@ -401,7 +410,7 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   // the guess cost more trips than it saved (7 % of the robots of a converged batch took 20-30 trips to repair a guess
   // where 1-10 trips from the unconstrained minimum do: profiles/ab_ppm_r06.txt, scripts/gpu_rollout_iters.py); a
   // controller that tracks its targets has next to nothing to guess anyway.
-  constexpr bool GUESS = PPX && PINKHIP_SWEEP_PPM_CRASH && !Src::kOnTheFly;
+  constexpr bool GUESS = (PPX && PINKHIP_SWEEP_PPM_CRASH && !Src::kOnTheFly) || WARM;
   if constexpr (GUESS) {
     // ---------------------------------------------------------------- principal pivoting: where it starts
     // Principal pivoting needs no feasibility of any kind from its starting basis, so it does not have to be the
@@ -414,8 +423,23 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
     // where it used to (scripts/multi_pivot_study.py).
     // (a non-positive diagonal entry: H is not positive definite whatever the rest looks like)
     if (group_first_lane<W>(in && !(hii > 0.0)) < W) status = STATUS_NOT_PD;
-    const double xd = -ci * approx_rcp(hii);
-    if (in) state = (xd < lbv) ? 1 : ((xd > ubv) ? 2 : 0);
+    if constexpr (WARM) {
+      // the caller's set where there is one (a kernel argument: wave-uniform), this kernel's own start where not: the
+      // diagonal guess in stack + solve, every coordinate free in the whole-step kernel
+      const uint8_t *hint = a.active_in;
+      if (hint) {
+        if (in) {
+          const int v = hint[b * (long long)nvs + NE + li];
+          state = (v == 1 && lbv > -INF) ? 1 : ((v == 2 && ubv < INF) ? 2 : 0);
+        }
+      } else if constexpr (!Src::kOnTheFly) {
+        const double xd = -ci * approx_rcp(hii);
+        if (in) state = (xd < lbv) ? 1 : ((xd > ubv) ? 2 : 0);
+      }
+    } else {
+      const double xd = -ci * approx_rcp(hii);
+      if (in) state = (xd < lbv) ? 1 : ((xd > ubv) ? 2 : 0);
+    }
     const unsigned long long fm = wave_ballot(li < NV && state == 0 && in);
     // this lane's group (W = 64: the wave, a scalar; below: 32 bits of a register)
     using FreeMask = typename std::conditional<W == 64, unsigned long long, unsigned>::type;
@@ -1264,6 +1288,17 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
         late->status[bw] = status;
         if (late->iters) late->iters[bw] = it + 1000 * why;  // (PATH_TABLEAU = 0; a group handed over is written again)
       }
+      if constexpr (WARM) {
+        // the final set, one byte per stated coordinate; all free for a group that failed (a failed step seeds nothing) or
+        // that is handed over (written again by the Goldfarb-Idnani code, from the working set it ends on)
+        uint8_t *const aout = late->active_out;
+        if (aout) {  // (wave-uniform)
+          if (in) aout[bw * (long long)nvs + NE + li] = static_cast<uint8_t>(status == STATUS_OPTIMAL ? state : 0);
+          if constexpr (NE > 0) {
+            if (li < NE) aout[bw * (long long)nvs + li] = 0;
+          }
+        }
+      }
     }
   }
   PINKHIP_TRACEF(li == 0, "[sweep g%d] exit status %d it %d nref %d\n", g, status, it, nref);
@@ -1279,9 +1314,9 @@ __host__ __device__ constexpr int sweep_kernel_lds_doubles(int md) {
 
 // (everything that touches the dynamic LDS must be inlined into the kernel: as a called function the body reached it
 // through a per-kernel offset table and faulted on the first access in the largest instantiations)
-template <int NV, int MD, int W>
+template <int NV, int MD, int W, bool WARM = false>
 __device__ __forceinline__ void ik_solve_sweep_body(const KernelArgs &a, long long block) {
-  const int st = ik_sweep_instance<NV, MD, W>(a, block);
+  const int st = ik_sweep_instance<NV, MD, W, HbmTerms, WARM>(a, block);
   // a result that did not pass its KKT certificate (STATUS_BREAKDOWN: the explicitly updated inverse lost too much
   // accuracy) is not handed out: the Goldfarb-Idnani kernel -- orthogonal factors, slower, stable -- solves that
   // instance again, here, in the same wavefront (wave-uniform branch: rare, weakly regularised objectives)
@@ -1311,11 +1346,11 @@ __device__ __forceinline__ void ik_solve_sweep_body(const KernelArgs &a, long lo
         const int pg = bcast_i(path, gg * W);
         if (og && blk * G + gg < again->B) {
           wave_sync();
-          ik_packed_instance<NV, kWave, false>(*again, blk * G + gg, static_cast<HbmTerms *>(nullptr), true, pg);
+          ik_packed_instance<NV, kWave, false, HbmTerms, WARM>(*again, blk * G + gg, static_cast<HbmTerms *>(nullptr), true, pg);
         }
       });
     } else {
-      ik_packed_instance<NV, W, (MD > 0)>(*again, blk, static_cast<HbmTerms *>(nullptr), over, st == STATUS_ROUTED ? PATH_ROUTED : PATH_HANDOVER);
+      ik_packed_instance<NV, W, (MD > 0), HbmTerms, WARM>(*again, blk, static_cast<HbmTerms *>(nullptr), over, st == STATUS_ROUTED ? PATH_ROUTED : PATH_HANDOVER);
     }
   }
 #endif
@@ -1324,6 +1359,12 @@ __device__ __forceinline__ void ik_solve_sweep_body(const KernelArgs &a, long lo
 template <int NV, int MD, int W>
 __global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_SWEEP3(NV, MD, W) ik_solve_sweep_kernel(KernelArgs a) {
   ik_solve_sweep_body<NV, MD, W>(a, block_id());
+}
+
+// ... started from the caller's active set (tu_wsweep.hip, PINKHIP_WSWEEP_TABLE): the budgets of the cold twin
+template <int NV, int MD, int W>
+__global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_SWEEP3(NV, MD, W) ik_solve_sweep_warm_kernel(KernelArgs a) {
+  ik_solve_sweep_body<NV, MD, W, true>(a, block_id());
 }
 
 }  // namespace pinkhip

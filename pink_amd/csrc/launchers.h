@@ -42,6 +42,16 @@ PINKHIP_ROLLOUT_TABLE(PINKHIP_DECLARE)
 PINKHIP_ROLLOUT_DENSE_TABLE(PINKHIP_DECLARE)
 #undef PINKHIP_DECLARE
 
+// tu_wsweep.hip / tu_wrollout.hip: the warm-start twins, one launcher per entry of PINKHIP_WSWEEP_TABLE / PINKHIP_WROLLOUT_TABLE
+#define PINKHIP_LAUNCH_WSWEEP_NAME(NV, MD, W) PINKHIP_PASTE6(launch_wsweep_, NV, MD, W)
+#define PINKHIP_DECLARE(NV, MD, W) hipError_t PINKHIP_LAUNCH_WSWEEP_NAME(NV, MD, W)(hipStream_t stream, const KernelArgs &a);
+PINKHIP_WSWEEP_TABLE(PINKHIP_DECLARE)
+#undef PINKHIP_DECLARE
+#define PINKHIP_LAUNCH_WROLLOUT_NAME(NV, W) PINKHIP_PASTE4(launch_wrollout_, NV, W)
+#define PINKHIP_DECLARE(NV, W) hipError_t PINKHIP_LAUNCH_WROLLOUT_NAME(NV, W)(hipStream_t stream, const RolloutArgs &a);
+PINKHIP_WROLLOUT_TABLE(PINKHIP_DECLARE)
+#undef PINKHIP_DECLARE
+
 
 
 

@@ -257,6 +257,15 @@ void set_problem(KernelArgs &a, const pinkhip_problem *in) {
   a.c_extra = in->c_extra;
 }
 
+// What the warm entry points refuse beyond the validation of their cold twins (empty: nothing)
+const char *warm_refusal(const pinkhip_desc *d, const KernelArgs &a) {
+  if (d->md > 0) return "warm starts are box-only (md == 0): dense rows run the dual method, which needs a dual-feasible start";
+  if (a.rank_deficient) return "the task stack is rank deficient by construction: it is solved by the Goldfarb-Idnani kernel, which takes no active set";
+  const char *solver_env = std::getenv("PINKHIP_SOLVER");
+  if (solver_env && std::strcmp(solver_env, "packed") == 0) return "PINKHIP_SOLVER=packed: the Goldfarb-Idnani kernel takes no active set";
+  return nullptr;
+}
+
 size_t align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
 int ensure_arena(pinkhip_handle *h, size_t bytes) {
@@ -424,6 +433,37 @@ int pinkhip_solve_device(pinkhip_handle *h, const pinkhip_desc *desc, const pink
   a.status = dev_out->status;
   a.iters = dev_out->iters;
   return launch(h, a, true);
+}
+
+int pinkhip_solve_warm_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_problem *dev_in,
+                              const pinkhip_result *dev_out, const pinkhip_warm *warm) {
+  KernelArgs a{};
+  int rc = prepare(h, desc, a);
+  if (rc) return rc;
+  if ((rc = check_problem(h, desc, dev_in))) return rc;
+  if (!dev_out || (desc->B > 0 && (!dev_out->dq || !dev_out->status)))
+    return fail(h, PINKHIP_E_INVALID, "dq/status must not be NULL");
+  if (!warm) return fail(h, PINKHIP_E_INVALID, "null warm-start arguments");
+  if (const char *why = warm_refusal(desc, a)) return fail(h, PINKHIP_E_UNSUPPORTED, why);
+  const pinkhip::SweepChoice sc = pinkhip::select_sweep_warm(a.nv, a.n_free_lead);
+  if (!sc.NV) return fail(h, PINKHIP_E_UNSUPPORTED, "no warm-start instantiation of the stack + solve kernel holds this nv");
+  if (a.B == 0) return PINKHIP_OK;
+  if (a.B > 0x7fffffffLL) return fail(h, PINKHIP_E_INVALID, "B exceeds the grid limit 2^31-1");
+  set_problem(a, dev_in);
+  a.dq = dev_out->dq;
+  a.status = dev_out->status;
+  a.iters = dev_out->iters;
+  a.active_in = warm->active_in;
+  a.active_out = warm->active_out;
+  hipError_t e = hipErrorInvalidValue;
+  switch (sc.NV * 100 + sc.W) {
+#define PINKHIP_CASE(NV, MD, W) \
+  case NV * 100 + W: e = pinkhip::PINKHIP_LAUNCH_WSWEEP_NAME(NV, MD, W)(h->stream, a); break;
+    PINKHIP_WSWEEP_TABLE(PINKHIP_CASE)
+#undef PINKHIP_CASE
+  }
+  PH_HIP(h, e);
+  return PINKHIP_OK;
 }
 
 int pinkhip_stack_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_problem *dev_in,
@@ -800,12 +840,18 @@ int pinkhip_step_device(pinkhip_handle *h, const pinkhip_model *m, int64_t B, co
   return PINKHIP_OK;
 }
 
-int pinkhip_rollout_step_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_model *m,
-                                const pinkhip_rollout_step *st) {
+// (warm: NULL = pinkhip_rollout_step_device; else the warm-start twin of the box-only whole-step kernel)
+static int rollout_step_launch(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_model *m, const pinkhip_rollout_step *st,
+                               const pinkhip_warm *warm) {
   if (!h || !m || !st) return fail(h, PINKHIP_E_INVALID, "null handle / model / args");
   pinkhip::RolloutArgs ra{};
   int rc = prepare(h, desc, ra.k);
   if (rc) return rc;
+  if (warm) {
+    if (const char *why = warm_refusal(desc, ra.k)) return fail(h, PINKHIP_E_UNSUPPORTED, why);
+    ra.k.active_in = warm->active_in;
+    ra.k.active_out = warm->active_out;
+  }
   const pinkhip::ModelDev &md = m->dev;
   if (desc->B == 0) return PINKHIP_OK;
   const int n_crow = st->n_const_rows;
@@ -860,7 +906,8 @@ int pinkhip_rollout_step_device(pinkhip_handle *h, const pinkhip_desc *desc, con
     ra.eq_gain = st->constraint_gain;
     ra.bar_frame2 = st->barrier_frame2;
   } else {
-    pc = pinkhip::select_rollout(md.nv, md.nj, fkd, st->n_const_rows > 0 || st->diag_error != nullptr || st->acc_limit != nullptr || m->image.has_relative);
+    pc = warm ? pinkhip::select_rollout_warm(md.nv, md.nj, fkd)
+              : pinkhip::select_rollout(md.nv, md.nj, fkd, st->n_const_rows > 0 || st->diag_error != nullptr || st->acc_limit != nullptr || m->image.has_relative);
     if (pc.NV == 0 || md.nf > 32) return fail(h, PINKHIP_E_UNSUPPORTED, "no whole-step instantiation fits this model");
     ra.k.lds_pitch = pinkhip::rollout_lds_doubles(pc.NV, pc.W, fkd);
   }
@@ -897,6 +944,13 @@ int pinkhip_rollout_step_device(pinkhip_handle *h, const pinkhip_desc *desc, con
       PINKHIP_ROLLOUT_DENSE_TABLE(PINKHIP_CASE)
 #undef PINKHIP_CASE
     }
+  } else if (warm) {
+    switch (pc.NV) {
+#define PINKHIP_CASE(NV, W) \
+  case NV: e = pinkhip::PINKHIP_LAUNCH_WROLLOUT_NAME(NV, W)(h->stream, ra); break;
+      PINKHIP_WROLLOUT_TABLE(PINKHIP_CASE)
+#undef PINKHIP_CASE
+    }
   } else {
     switch (pc.NV) {
 #define PINKHIP_CASE(NV, W) \
@@ -907,6 +961,17 @@ int pinkhip_rollout_step_device(pinkhip_handle *h, const pinkhip_desc *desc, con
   }
   PH_HIP(h, e);
   return PINKHIP_OK;
+}
+
+int pinkhip_rollout_step_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_model *m,
+                                const pinkhip_rollout_step *st) {
+  return rollout_step_launch(h, desc, m, st, nullptr);
+}
+
+int pinkhip_rollout_step_warm_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_model *m,
+                                     const pinkhip_rollout_step *st, const pinkhip_warm *warm) {
+  if (!warm) return fail(h, PINKHIP_E_INVALID, "null warm-start arguments");
+  return rollout_step_launch(h, desc, m, st, warm);
 }
 
 int pinkhip_limits_posture_device(pinkhip_handle *h, const pinkhip_model *m, int64_t B, double dt,

@@ -1,0 +1,23 @@
+// Warm-start twins of the tableau kernels under the CPU wave emulator -- TEST INFRASTRUCTURE ONLY (see wave_emu.h).
+// Additive to emu_lanes.h / emu_registry.h: two registry kinds of their own and the per-lane entry points of
+// ik_solve_sweep_warm_kernel / ik_rollout_warm_kernel (tu_wsweep.hip / tu_wrollout.hip).
+#pragma once
+#include "emu_lanes.h"
+
+namespace pinkemu {
+
+// (behind the kinds of emu_registry.h: the registry is keyed by plain integers)
+constexpr int KIND_SWEEP_WARM = 100, KIND_ROLLOUT_WARM = 101;
+
+template <int NV, int MD, int W>
+void lane_main_sweep_warm(void *p) {
+  KernelArgs k = *static_cast<const KernelArgs *>(p);
+  k.lds_pitch = pinkhip::sweep_kernel_lds_doubles<NV, MD, W>(0);  // as tu_wsweep.hip's launcher
+  pinkhip::ik_solve_sweep_body<NV, MD, W, true>(k, pinkhip::block_id());
+}
+template <int NV, int W>
+void lane_main_rollout_warm(void *p) {
+  pinkhip::ik_rollout_instance<NV, 0, W, true>(*static_cast<const pinkhip::RolloutArgs *>(p), pinkhip::block_id());
+}
+
+}  // namespace pinkemu

@@ -1,0 +1,38 @@
+// One slice of the warm-start instantiations of the CPU wave emulator -- TEST INFRASTRUCTURE ONLY.
+//   g++ -c -DEMU_PART=k -DEMU_NPARTS=n emu_warm_part.cpp    for k = 0 .. n-1 (built in parallel, like emu_part.cpp)
+#include "emu_warm.h"
+
+#ifndef EMU_PART
+#define EMU_PART 0
+#endif
+#ifndef EMU_NPARTS
+#define EMU_NPARTS 1
+#endif
+
+namespace {
+
+// (the entries of the two tables are dealt out in turn: nine heavy instantiations over the slices)
+template <int P, int I>
+constexpr bool mine() {
+  return (I % EMU_NPARTS) == P;
+}
+
+template <int P>
+void register_slice() {
+  using namespace pinkemu;
+  constexpr int base = __COUNTER__ + 1;
+#define PINKHIP_CASE(NV, MD, W) \
+  if constexpr (mine<P, __COUNTER__ - base>()) emu_register(KIND_SWEEP_WARM, NV, MD, W, &lane_main_sweep_warm<NV, MD, W>);
+  PINKHIP_WSWEEP_TABLE(PINKHIP_CASE)
+#undef PINKHIP_CASE
+#define PINKHIP_CASE(NV, W) \
+  if constexpr (mine<P, __COUNTER__ - base>()) emu_register(KIND_ROLLOUT_WARM, NV, 0, W, &lane_main_rollout_warm<NV, W>);
+  PINKHIP_WROLLOUT_TABLE(PINKHIP_CASE)
+#undef PINKHIP_CASE
+}
+
+struct Registrar {
+  Registrar() { register_slice<EMU_PART>(); }
+} registrar;
+
+}  // namespace
