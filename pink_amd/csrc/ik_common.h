@@ -46,6 +46,29 @@ __device__ __forceinline__ void static_for(F &&f) {
     static_for<I + 1, N>(f);
   }
 }
+// t + d in lane J of every group of W lanes, t itself in all the others (whatever d holds there).  J is a compile-time
+// index, so "lane J of every group" is a literal lane mask: the add runs with the other lanes switched off (EXEC), one
+// VALU instruction, instead of a compare and two selects around it.
+template <int W, int J>
+__device__ __forceinline__ double add_in_lane(double t, double d) {
+  static_assert((W == 16 || W == 32 || W == 64) && J >= 0 && J < W, "lane of a group of whole rows of 16 lanes");
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr unsigned long long one = 1ull << J;
+  constexpr unsigned long long m = W == 64 ? one : W == 32 ? one | (one << 32) : one | (one << 16) | (one << 32) | (one << 48);
+  unsigned slo, shi;  // (the lanes that are on at the call stay the only ones that can be)
+  asm("s_mov_b32 %1, exec_lo\n\ts_mov_b32 %2, exec_hi\n\t"
+      "s_and_b32 exec_lo, %1, %4\n\ts_and_b32 exec_hi, %2, %5\n\t"
+      "v_add_f64 %0, %0, %3\n\t"
+      "s_mov_b32 exec_lo, %1\n\ts_mov_b32 exec_hi, %2"
+      : "+v"(t), "=&s"(slo), "=&s"(shi)
+      : "v"(d), "n"(static_cast<int>(m & 0xFFFFFFFFull)), "n"(static_cast<int>(m >> 32))
+      : "scc");
+  return t;
+#else
+  return ((lane_id() & (W - 1)) == J) ? t + d : t;
+#endif
+}
+
 // "Transpose-reduce": every lane of a group holds N <= W partial values v(0..N-1); afterwards lane j of the group
 // holds sum over the group's lanes of v(j) (lanes >= N: 0).  Recursive halving: at level b the lanes whose bit b
 // is set keep the odd entries and hand the even ones to their partner (lane ^ 2^b), and vice versa, so the number

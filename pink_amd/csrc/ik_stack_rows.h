@@ -49,16 +49,42 @@ struct StackFront {
   double hxx[NX > 0 ? NX * (NX + 1) / 2 : 1] = {};
   double cx[NX > 0 ? NX : 1] = {};
 };
-template <int NV, int W, int RCMAX, class Src, int DEPTH = 1, int NX = 0, int NM, class Mid = NoMid>
+// Where the instances of a wave sit in the batch (SPLIT below): the first one, `first` -- the same in every lane, so that
+// whatever is formed from it and from kernel arguments is scalar arithmetic on a scalar pointer -- and this lane's
+// instance counted from it, `rel` (0 .. 64 / W - 1).  A lane's entry of a [B, pitch] stream is then
+// (stream + first * pitch)[rel * pitch + li]: a scalar base and ONE 32-bit offset per lane, whatever the pitch, in the
+// place of a 64-bit product and sum per lane and request.
+struct WaveSplit {
+  long long first = 0;
+  unsigned rel = 0;
+};
+// ... for the sources that read their terms from HBM.  The whole-step kernel reads next to nothing per instance here (its
+// rows are formed on chip) and holds the state of its kinematics in scalar registers at this point: the scalar bases were
+// registers it did not have (spilled SGPRs in most of its instantiations), so it keeps the per-lane addresses.
+#ifndef PINKHIP_WAVE_SPLIT
+#define PINKHIP_WAVE_SPLIT(Src) (!Src::kOnTheFly)
+#endif
+// DIAG: *hdiag follows this lane's own diagonal entry M[li] (lane li, li < NV) in a register of its own -- the product the
+// broadcast-FMA of column li forms in lane li is this lane's own row entry times its own factor: the same FMA on the
+// same operands, bit for bit what M[li] receives -- so that the caller does not have to pick "register li of lane li"
+// out of the row afterwards (NV compares and 2 NV selects).  It also takes the instance as `ws` (b = ws.first + ws.rel)
+// and addresses the streams as described at WaveSplit: the same addresses.  Off: nothing changes.
+template <int NV, int W, int RCMAX, class Src, int DEPTH = 1, int NX = 0, bool DIAG = false, int NM, class Mid = NoMid>
 __device__ __forceinline__ void stack_rows_bcast(const KernelArgs &a, long long b, Src *terms, bool in, int li,
-                                                 double (&M)[NM], double &ci, double &mu_l, Mid mid = Mid(), StackFront<NX> *front = nullptr) {
+                                                 double (&M)[NM], double &ci, double &mu_l, Mid mid = Mid(), StackFront<NX> *front = nullptr,
+                                                 double *hdiag = nullptr, WaveSplit ws = WaveSplit()) {
   static_assert(NX >= 0 && NX <= 2 && (NX == 0 || !Src::kOnTheFly), "at most two front columns, from HBM");
   static_assert(NM >= NV && W >= 16, "row-group kernels only");
   using BcT = Bcast<W>;
   const int nv = a.nv, Kd = a.Kd, K = a.K;
-  const double *Jb = a.J + b * (long long)Kd * nv;
-  const double *eb = a.e + b * (long long)K;
-  const double *costb = a.cost_batched ? a.cost + b * (long long)K : a.cost;
+  // (SPLIT: the scalar bases of the wave and this lane's offsets from them; a.cost is per instance or one for all)
+  constexpr bool SPLIT = DIAG && PINKHIP_WAVE_SPLIT(Src);
+  const double *Jb = a.J + (SPLIT ? ws.first : b) * (long long)Kd * nv;
+  const double *eb = a.e + (SPLIT ? ws.first : b) * (long long)K;
+  const double *costb = a.cost_batched ? a.cost + (SPLIT ? ws.first : b) * (long long)K : a.cost;
+  const unsigned voJ = SPLIT ? ws.rel * static_cast<unsigned>(Kd * nv) + li : 0u;
+  const unsigned voE = SPLIT ? ws.rel * static_cast<unsigned>(K) + li : 0u;
+  const unsigned voC = (SPLIT && a.cost_batched) ? voE : static_cast<unsigned>(li);
   constexpr int RC = Src::kOnTheFly ? 6 : (RCMAX < 8 ? RCMAX : 8);
   constexpr int NB = Src::kOnTheFly ? 2 : DEPTH + 1;  // chunk buffers: the one being accumulated + those in flight
   static_assert(RC <= 16, "weight rows are broadcast from the first row of 16 lanes");
@@ -77,20 +103,34 @@ __device__ __forceinline__ void stack_rows_bcast(const KernelArgs &a, long long 
       for (int kk = 0; kk < RC; ++kk) dst.r[kk] = (in && kk < rc) ? six[kk] : 0.0;
     } else {
 #pragma unroll
-      for (int kk = 0; kk < RC; ++kk) dst.r[kk] = (in && kk < rc) ? Jb[(long long)(r0 + kk) * nv + li] : 0.0;
+      for (int kk = 0; kk < RC; ++kk) {
+        if constexpr (SPLIT) dst.r[kk] = (in && kk < rc) ? (Jb + (long long)(r0 + kk) * nv)[voJ] : 0.0;
+        else dst.r[kk] = (in && kk < rc) ? Jb[(long long)(r0 + kk) * nv + li] : 0.0;
+      }
     }
     dst.pw = dst.pe = dst.pg = dst.pl = 0.0;
     if constexpr (NX > 0) {
 #pragma unroll
-      for (int x = 0; x < NX; ++x) dst.px[x] = (li < rc) ? Jb[(long long)(r0 + li) * nv - NX + x] : 0.0;
+      for (int x = 0; x < NX; ++x) {
+        if constexpr (SPLIT) dst.px[x] = (li < rc) ? (Jb + ((long long)r0 * nv - NX + x))[voJ - li + static_cast<unsigned>(li * nv)] : 0.0;
+        else dst.px[x] = (li < rc) ? Jb[(long long)(r0 + li) * nv - NX + x] : 0.0;
+      }
     }
     if (li < rc) {
       const int k = r0 + li;
-      dst.pw = costb[k];
-      if constexpr (Src::kOnTheFly) dst.pe = terms->error(k);
-      else dst.pe = eb[k];
-      dst.pg = a.row_gain[k];
-      dst.pl = a.row_lm[k];
+      if constexpr (SPLIT) {
+        dst.pw = (costb + r0)[voC];
+        if constexpr (Src::kOnTheFly) dst.pe = terms->error(k);
+        else dst.pe = (eb + r0)[voE];
+        dst.pg = (a.row_gain + r0)[static_cast<unsigned>(li)];
+        dst.pl = (a.row_lm + r0)[static_cast<unsigned>(li)];
+      } else {
+        dst.pw = costb[k];
+        if constexpr (Src::kOnTheFly) dst.pe = terms->error(k);
+        else dst.pe = eb[k];
+        dst.pg = a.row_gain[k];
+        dst.pl = a.row_lm[k];
+      }
     }
   };
   if (Kd > 0) {
@@ -126,6 +166,7 @@ __device__ __forceinline__ void stack_rows_bcast(const KernelArgs &a, long long 
         // (the row's own uses first: the row copies of the broadcast are then made in its registers)
         const double aa = fma_bcast<W, kk>(0.0, wab, cur.r[kk]);
         ci = fma_bcast<W, kk>(ci, gwb, cur.r[kk]);
+        if constexpr (DIAG) *hdiag = fma(cur.r[kk], aa, *hdiag);
         const BcT rowb = bcast_prepare<W>(cur.r[kk]);
         static_for<0, NV>([&](auto Jc) {
           constexpr int j = decltype(Jc)::value;
@@ -158,6 +199,32 @@ __device__ __forceinline__ double stack_diag_tasks(const KernelArgs &a, long lon
       double ev;
       if constexpr (Src::kOnTheFly) ev = terms->diag_error(r);
       else ev = eb[r];
+      const double wa = w * w;
+      dadd += wa;
+      ci += gn * wa * ev;
+      mu_l += l * (gn * gn) * wa * ev * ev;
+    }
+  }
+  return dadd;
+}
+
+// ... with the instance as a WaveSplit: the same terms from the same addresses
+template <class Src>
+__device__ __forceinline__ double stack_diag_tasks(const KernelArgs &a, WaveSplit ws, Src *terms, int li, double &ci,
+                                                   double &mu_l) {
+  const double *eb = a.e + ws.first * (long long)a.K;
+  const double *costb = a.cost_batched ? a.cost + ws.first * (long long)a.K : a.cost;
+  const unsigned vo = ws.rel * static_cast<unsigned>(a.K);
+  const unsigned voc = a.cost_batched ? vo : 0u;
+  double dadd = 0.0;
+  for (int t = 0; t < a.n_dtasks; ++t) {
+    const int off = li - a.dtask_col0[t];
+    if (off >= 0 && off < a.dtask_k[t]) {
+      const int r = a.dtask_row0[t] + off;
+      const double w = costb[voc + static_cast<unsigned>(r)], gn = a.row_gain[r], l = a.row_lm[r];
+      double ev;
+      if constexpr (Src::kOnTheFly) ev = terms->diag_error(r);
+      else ev = eb[vo + static_cast<unsigned>(r)];
       const double wa = w * w;
       dadd += wa;
       ci += gn * wa * ev;

@@ -125,6 +125,19 @@ static __device__ unsigned long long pinkhip_clock[16];  // one copy per transla
 #define PINKHIP_SWEEP_PPM_MURTY_AFTER(nv) (4 * (nv) + 20)
 #endif
 
+// A lane's own diagonal entry in a register of its own from the first stacked row on (0: picked out of the row with
+// compares and selects where it is needed, as the whole-step kernel still does: it is short of registers where its
+// kinematics state is live next to the stacking -- the extra register and the scalar temporaries of add_in_lane were
+// three more spilled VGPRs at nv = 30 and eight more spilled SGPRs at nv = 16)
+#ifndef PINKHIP_SWEEP_DIAG_REGISTER
+#define PINKHIP_SWEEP_DIAG_REGISTER(Src) (!Src::kOnTheFly)
+#endif
+// the LDS addresses of the closing product formed inside the closing trips (krow_times), not in front of the loop
+// (the whole-step kernel: eight more spilled SGPRs at nv = 16 -- as before there)
+#ifndef PINKHIP_SWEEP_LATE_ADDRESSES
+#define PINKHIP_SWEEP_LATE_ADDRESSES(Src) (!Src::kOnTheFly)
+#endif
+
 namespace pinkhip {
 
 // LDS of one QP (doubles): the stated problem, parked for the closing refinement step
@@ -166,6 +179,7 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   constexpr int NT = NV + MD;
   static_assert((W == 16 || W == 32 || W == 64) && NT <= W && NV % 2 == 0 && MD >= 0, "group of whole rows of 16 lanes");
   constexpr bool DENSE = MD > 0;
+  constexpr bool DREG = PINKHIP_SWEEP_DIAG_REGISTER(Src);
   constexpr bool PPM = !DENSE && PINKHIP_SWEEP_PPM;                                  // box-only: the whole iteration
   constexpr bool PPMD = DENSE && PINKHIP_SWEEP_PPM && PINKHIP_SWEEP_PPM_DENSE && (!Src::kOnTheFly || PINKHIP_ROLLOUT_PPM_DENSE);  // dense rows: in front of the dual method
   constexpr bool PPX = PPM || PPMD;
@@ -187,6 +201,12 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   long long b = block * G + g;
   const bool valid = b < a.B;
   if (!valid) b = a.B - 1;  // surplus groups of the last wave redo the last instance, write nothing
+  // the same index as a scalar part and a small per-lane part (ik_stack_rows.h, WaveSplit): the streams are addressed
+  // with a scalar base and one 32-bit offset per lane
+  WaveSplit ws;
+  ws.first = (block * G < a.B - 1) ? block * G : a.B - 1;  // (wave-uniform)
+  ws.rel = static_cast<unsigned>(b - ws.first);
+  const unsigned vo = ws.rel * static_cast<unsigned>(nvs) + li;  // this lane's entry of a [B, nvs] stream, from first * nvs + NE
 
   const bool in = li < nv;          // coordinate lane
   const int dr = li - NV;           // dense row of this lane
@@ -207,11 +227,16 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   auto others = [&]() {
     if (in) {
       if constexpr (!Src::kOnTheFly) {
-        lbv = a.lb[b * (long long)nvs + NE + li];
-        ubv = a.ub[b * (long long)nvs + NE + li];
+        lbv = (a.lb + (ws.first * (long long)nvs + NE))[vo];
+        ubv = (a.ub + (ws.first * (long long)nvs + NE))[vo];
       }
-      dadd = stack_diag_tasks<Src>(a, b, terms, NE + li, ci_d, mu_d);
-      if (a.c_extra) ci_d += a.c_extra[b * (long long)nvs + NE + li];
+      if constexpr (PINKHIP_WAVE_SPLIT(Src)) dadd = stack_diag_tasks<Src>(a, ws, terms, NE + li, ci_d, mu_d);
+      else dadd = stack_diag_tasks<Src>(a, b, terms, NE + li, ci_d, mu_d);
+      if constexpr (PINKHIP_WAVE_SPLIT(Src)) {
+        if (a.c_extra) ci_d += (a.c_extra + (ws.first * (long long)nvs + NE))[vo];
+      } else {
+        if (a.c_extra) ci_d += a.c_extra[b * (long long)nvs + NE + li];
+      }
     }
     if constexpr (NE > 0) {
 #pragma unroll
@@ -236,12 +261,15 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
     }
   };
   StackFront<NE> front;
+  // H[li][li], this lane's own diagonal entry: followed in a register of its own from the first stacked row on (the same
+  // FMAs on the same operands as the copy inside the row) -- "register li of lane li" is never picked out of T
+  double hii = 0.0;
   if constexpr (NE > 0) {
     KernelArgs af = a;  // (the rows as the lanes see them: NE columns in)
     af.J = a.J + NE;
-    stack_rows_bcast<NV, W, 8, Src, PINKHIP_STACK_DEPTH, NE>(af, b, terms, in, li, T, ci, mu_l, others, &front);
+    stack_rows_bcast<NV, W, 8, Src, PINKHIP_STACK_DEPTH, NE, DREG>(af, b, terms, in, li, T, ci, mu_l, others, &front, &hii, ws);
   } else {
-    stack_rows_bcast<NV, W, 8, Src, (NT > 34 ? PINKHIP_STACK_DEPTH_WIDE : PINKHIP_STACK_DEPTH)>(a, b, terms, in, li, T, ci, mu_l, others);
+    stack_rows_bcast<NV, W, 8, Src, (NT > 34 ? PINKHIP_STACK_DEPTH_WIDE : PINKHIP_STACK_DEPTH), 0, DREG>(a, b, terms, in, li, T, ci, mu_l, others, nullptr, &hii, ws);
   }
   ci += ci_d;
   mu_l += mu_d;
@@ -303,13 +331,22 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   }
   const double diag_u = diag;  // (the part every coordinate gets: damping + the Levenberg-Marquardt terms + barrier objective)
   diag += dadd;  // (per lane from here on: what H[li][li] holds beyond the dense task rows; kept for the refinement)
-  double hii = 1.0;  // H[li][li]
+  if constexpr (DREG) {
+    const double dd = in ? diag : 1.0;  // padded coordinates: identity rows, never pivoted
+    static_for<0, NV>([&](auto Jc) {
+      constexpr int j = decltype(Jc)::value;
+      T[j] = add_in_lane<W, j>(T[j], dd);
+    });
+    hii += dd;  // (lanes behind the coordinates: 1, as before)
+  } else {
+    hii = 1.0;
 #pragma unroll
-  for (int j = 0; j < NV; ++j)
-    if (j == li) {
-      T[j] += in ? diag : 1.0;  // padded coordinates: identity rows, never pivoted
-      hii = T[j];
-    }
+    for (int j = 0; j < NV; ++j)
+      if (j == li) {
+        T[j] += in ? diag : 1.0;
+        hii = T[j];
+      }
+  }
   using SL = SweepLds<NV, MD, W>;
   double *sm = shared_base() + (long long)g * (a.lds_pitch ? a.lds_pitch : SL::stride);
   // ------------------------------------------------------------------ front coordinates out of the problem
@@ -411,6 +448,9 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   // where 1-10 trips from the unconstrained minimum do: profiles/ab_ppm_r06.txt, scripts/gpu_rollout_iters.py); a
   // controller that tracks its targets has next to nothing to guess anyway.
   constexpr bool GUESS = (PPX && PINKHIP_SWEEP_PPM_CRASH && !Src::kOnTheFly) || WARM;
+  // The diagonal entry of a lane's own row through the initial sweeps: sweep k makes T[li][li] + T[li][k] nt of it in lane
+  // li (the broadcast-FMA of column li: the same operands) and -1 / p in lane k.  (the lane of a dense row starts at 0)
+  double tdiag = (li < NV) ? hii : 0.0;
   if constexpr (GUESS) {
     // ---------------------------------------------------------------- principal pivoting: where it starts
     // Principal pivoting needs no feasibility of any kind from its starting basis, so it does not have to be the
@@ -458,6 +498,10 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
           const double p = value_bcast<W, k>(xb);
           pmin = min_raw(pmin, want ? p : INF);
           const double rp = fast_rcp(p);
+          // (this lane's entry of column k once more, for the diagonal register below: a copy of its own, so that the
+          // entry itself is rescaled in its register -- left to the allocator the copy became a rotation of the whole row)
+          double own = T[k];
+          if constexpr (DREG) opaque(own);
           const double t = T[k] * rp;
           double nt = (li == k) ? rp - 1.0 : -t;
           if (!want) nt = 0.0;
@@ -467,11 +511,14 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
           // rotated the whole row through its registers around each sweep of the whole-step kernel -- 30 moves per sweep)
           asm volatile("" : "+v"(nt), "+v"(xb.r[0]), "+v"(tk));
 #endif
+          double td = 0.0;
+          if constexpr (DREG) td = fma(own, nt, tdiag);  // (own entry times own factor: what the FMA of column li makes of it)
           static_for<0, NT>([&](auto Jc) {
             constexpr int j = decltype(Jc)::value;
             if constexpr (j != k) T[j] = fma_bcast<W, j>(T[j], xb, nt);
           });
           if (want) T[k] = tk;
+          if constexpr (DREG) tdiag = (li == k) ? T[k] : td;
         }
       }
     });
@@ -490,6 +537,7 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
           constexpr int j = decltype(Jc)::value;
           if constexpr (j != k) T[j] = fma_bcast<W, j>(T[j], xb, nt);
         });
+        if constexpr (DREG) tdiag = (li == k) ? -rp : fma(T[k], nt, tdiag);
         T[k] = (li == k) ? -rp : t;
       }
     });
@@ -498,10 +546,14 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   PINKHIP_TICK(1);  // initial sweeps
   // The diagonal entry of a lane's own row: kept in a register of its own from here on (a pivot on a run-time index
   // cannot address "register p of lane p"; the copy inside T is not maintained and never read).
-  double tdiag = 0.0;
+  if constexpr (DREG) {
+    if (li >= NT) tdiag = 0.0;  // (lanes behind the tableau hold no entry of it)
+  } else {
+    tdiag = 0.0;
 #pragma unroll
-  for (int j = 0; j < NT; ++j)
-    if (j == li) tdiag = T[j];
+    for (int j = 0; j < NT; ++j)
+      if (j == li) tdiag = T[j];
+  }
 
   // x0 = -H^-1 c = T_BB c; the same product gives the rows of G: slack = h - G x0 = h + (T c)_row
   // (principal pivoting from a guessed active set: with v = c on the free coordinates and -bound on the fixed ones the
@@ -623,12 +675,29 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   // coordinate lanes parked)
   auto krow_times = [&](double v) -> double {
     const BcT vb = bcast_prepare<W>(v);
-    const int base = (li < NV) ? SL::tri(li) : SL::oG + (dlane ? dr : 0) * SL::GP;
+    // Two bases per lane -- its row of the triangle (resp. its row of G) and its column -- and per j one add, one compare
+    // and one select in front of a read whose constant part, tri(j), sits in the instruction's offset field.  The lane
+    // index is opaque here: the addresses are formed where they are used, inside the closing trips, instead of being
+    // hoisted in front of the tableau loop and kept in registers across it.
+    // (off -- the whole-step kernel: one index per j from the lane index, as hoisted as the compiler likes)
+    constexpr bool LATE = PINKHIP_SWEEP_LATE_ADDRESSES(Src);
+    int lo_ = li;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (LATE) asm volatile("" : "+v"(lo_));
+#endif
+    const int base = (lo_ < NV) ? SL::tri(lo_) : SL::oG + (dlane ? dr : 0) * SL::GP;
+    const double *const rowp = sm + base, *const colp = sm + lo_;
     double h0 = 0.0, h1 = 0.0;
     static_for<0, NV>([&](auto Jc) {
       constexpr int j = decltype(Jc)::value;
-      const int ad = (li < NV && j > li) ? SL::tri(j) + li : base + j;
-      const double hv_ = sm[ad];
+      // (j > li: H[j][li] at tri(j) + li; else H[li][j] resp. G[d][j] at base + j)
+      double hv_;
+      if constexpr (LATE) {
+        const double *const pj = (j > lo_) ? colp : rowp + (j - SL::tri(j));
+        hv_ = pj[SL::tri(j)];
+      } else {
+        hv_ = sm[(li < NV && j > li) ? SL::tri(j) + li : base + j];
+      }
       if constexpr (j % 2 == 0) h0 = fma_bcast<W, j>(h0, vb, hv_);
       else h1 = fma_bcast<W, j>(h1, vb, hv_);
     });
@@ -1270,7 +1339,11 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+v"(ln));
 #endif
-    const long long bw = block * G + ln / W;
+    // (a scalar first instance and a per-lane group number: scalar bases, one 32-bit offset per lane -- WaveSplit)
+    const long long bw0 = block * G;
+    const unsigned gw = static_cast<unsigned>(ln) / W;
+    const long long bw = bw0 + gw;
+    const unsigned vow = gw * static_cast<unsigned>(nvs) + li;
     // the eliminated front coordinates follow from the point: x_e = -(c_e + h_e . x + H_ee' x_e') / H_ee, last one first
     double xe[NE > 0 ? NE : 1] = {};
     if constexpr (NE > 0) {
@@ -1280,13 +1353,21 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
       xe[0] = -(fs[0] + group_sum<W>(sm[SL::stride + li] * xr) + ((NE == 2) ? fs[2] * xe[NE - 1] : 0.0)) * fs[1];
     }
     if (bw < late->B) {
-      if (in) late->dq[bw * (long long)nvs + NE + li] = x * late->out_scale;
-      if constexpr (NE > 0) {
-        if (li < NE) late->dq[bw * (long long)nvs + li] = ((li == 0) ? xe[0] : xe[NE - 1]) * late->out_scale;
-      }
-      if (li == 0) {
-        late->status[bw] = status;
-        if (late->iters) late->iters[bw] = it + 1000 * why;  // (PATH_TABLEAU = 0; a group handed over is written again)
+      if constexpr (PINKHIP_WAVE_SPLIT(Src)) {
+        if (in) (late->dq + (bw0 * (long long)nvs + NE))[vow] = x * late->out_scale;
+        if constexpr (NE > 0) {
+          if (li < NE) (late->dq + bw0 * (long long)nvs)[vow] = ((li == 0) ? xe[0] : xe[NE - 1]) * late->out_scale;
+        }
+        if (li == 0) {
+          (late->status + bw0)[gw] = status;
+          if (late->iters) (late->iters + bw0)[gw] = it + 1000 * why;  // (PATH_TABLEAU = 0; a group handed over is written again)
+        }
+      } else {
+        if (in) late->dq[bw * (long long)nvs + NE + li] = x * late->out_scale;
+        if (li == 0) {
+          late->status[bw] = status;
+          if (late->iters) late->iters[bw] = it + 1000 * why;
+        }
       }
       if constexpr (WARM) {
         // the final set, one byte per stated coordinate; all free for a group that failed (a failed step seeds nothing) or
