@@ -23,6 +23,7 @@
 #include "ik_rollout.h"
 #include "host_tables.h"
 #include "model_tables.h"
+#include "host_plan.h"
 // clang-format on
 
 namespace {
@@ -78,6 +79,7 @@ int fail(pinkhip_handle *h, int code, const std::string &msg) {
   } while (0)
 
 using pinkhip::KernelArgs;
+using pinkhip::LaunchPlan;
 
 // ncclUniqueId is passed by value to ncclCommInitRank: same layout, no RCCL header needed
 struct pinkhip_unique_id_t {
@@ -98,79 +100,71 @@ int launch_stack_mfma(pinkhip_handle *h, const KernelArgs &a) {
   return PINKHIP_OK;
 }
 
-int launch(pinkhip_handle *h, const KernelArgs &a, bool solve) {
-  if (a.B == 0) return PINKHIP_OK;
-  if (a.B > 0x7fffffffLL) return fail(h, PINKHIP_E_INVALID, "B exceeds the grid limit 2^31-1");
-  if (!solve) {  // stack only: fp64 MFMA tiles, NT = ceil(nv / 16)
-    if (a.nv <= 8 && a.n_barriers == 0) {
-      // two instances per MFMA tile; four tiles per wavefront once that still leaves >= 32 waves per CU
-      // (measured, UR5: 24 us instead of 51 us at B = 65 536, but 6.4 instead of 5.1 us at B = 4 096)
-      const dim3 block(pinkhip::kWave);
-      if (a.B >= 65536) {
-        hipLaunchKernelGGL(pinkhip::ik_stack_small_kernel<4>, dim3(static_cast<unsigned>((a.B + 7) / 8)), block, 0, h->stream, a);
+// Launch what host_plan.h planned for `a` (stack only, stack + solve, or its warm-start twin): each instantiation of the
+// stack + solve kernels is its own translation unit, reached through the launcher tables of launchers.h.
+int launch(pinkhip_handle *h, const KernelArgs &a, bool solve, bool warm = false) {
+  static const bool force_dense = std::getenv("PINKHIP_FORCE_DENSE") != nullptr;  // development: time the dense-row instantiation on a batch without dense rows
+  LaunchPlan p;
+  std::string why;
+  // stack only, nv <= 8: four tiles per wavefront once that still leaves >= 32 waves per CU
+  // (measured, UR5: 24 us instead of 51 us at B = 65 536, but 6.4 instead of 5.1 us at B = 4 096)
+  const int rc = solve ? pinkhip::plan_solve(a, std::getenv("PINKHIP_SOLVER"), force_dense, warm, p, why) : pinkhip::plan_stack(a, a.B >= 65536, p, why);
+  if (rc) return fail(h, rc, why);
+  const dim3 grid(static_cast<unsigned>(p.blocks)), block(pinkhip::kWave);
+  hipError_t e = hipErrorInvalidValue;  // (a plan without a launcher)
+  switch (p.kind) {
+    case pinkhip::PLAN_NONE: return PINKHIP_OK;
+    case pinkhip::PLAN_STACK_SMALL:
+      if (p.W == 8) {
+        hipLaunchKernelGGL(pinkhip::ik_stack_small_kernel<4>, grid, block, 0, h->stream, a);
       } else {
-        hipLaunchKernelGGL(pinkhip::ik_stack_small_kernel<1>, dim3(static_cast<unsigned>((a.B + 1) / 2)), block, 0, h->stream, a);
+        hipLaunchKernelGGL(pinkhip::ik_stack_small_kernel<1>, grid, block, 0, h->stream, a);
       }
       PH_HIP(h, hipGetLastError());
       return PINKHIP_OK;
-    }
-    switch ((a.nv + 15) / 16) {
-      case 1: return launch_stack_mfma<1>(h, a);
-      case 2: return launch_stack_mfma<2>(h, a);
-      case 3: return launch_stack_mfma<3>(h, a);
-      case 4: return launch_stack_mfma<4>(h, a);
-    }
-    return fail(h, PINKHIP_E_INVALID, "unsupported nv");
-  }
-  // stack + solve: the instantiation chosen by dispatch.h, each one its own translation unit.  The sweep-tableau
-  // kernel (ik_sweep.h, tu_sweep.hip) serves every problem it is instantiated for; the Goldfarb-Idnani kernel
-  // (ik_kernels_packed.h, tu_packed.hip) the rest: 8-lane groups (nv <= 8), more dense rows than lanes are left.
-  const char *solver_env = std::getenv("PINKHIP_SOLVER");  // development / tests: "packed" / "sweep" force one kernel
-  const pinkhip::SweepChoice sc = pinkhip::select_sweep(a.nv, a.md, a.n_free_lead);
-  const bool sweep = solver_env ? (std::strcmp(solver_env, "packed") != 0 && sc.NV != 0)
-                                : (pinkhip::prefer_sweep(a.nv, a.md, a.B, a.n_free_lead) && !a.rank_deficient);
-  // ... with virtual dense rows where that packs more QPs into a wavefront (ik_sweepx.h, dispatch.h prefer_sweepx)
-  const pinkhip::SweepChoice xc = pinkhip::select_sweepx(a.nv, a.md);
-  const bool sweepx = solver_env ? (std::strcmp(solver_env, "sweepx") == 0 && xc.NV != 0)
-                                 : (pinkhip::prefer_sweepx(a.nv, a.md) && !a.rank_deficient);
-  if (sweepx) {
-    hipError_t ex = hipErrorInvalidValue;
-    switch (xc.NV * 100 + xc.MD) {
-#define PINKHIP_CASE(NV, MD, W)                                            \
-  case NV * 100 + MD:                                                      \
-    ex = pinkhip::PINKHIP_LAUNCH_SWEEPX_NAME(NV, MD, W)(h->stream, a);     \
-    break;
-      PINKHIP_SWEEPX_TABLE(PINKHIP_CASE)
+    case pinkhip::PLAN_STACK_MFMA:
+      switch (p.NV / 16) {
+        case 1: return launch_stack_mfma<1>(h, a);
+        case 2: return launch_stack_mfma<2>(h, a);
+        case 3: return launch_stack_mfma<3>(h, a);
+        case 4: return launch_stack_mfma<4>(h, a);
+      }
+      break;
+    case pinkhip::PLAN_SWEEPX:
+      switch (p.NV * 100 + p.MD) {
+#define PINKHIP_CASE(NV, MD, W) \
+  case NV * 100 + MD: e = pinkhip::PINKHIP_LAUNCH_SWEEPX_NAME(NV, MD, W)(h->stream, a); break;
+        PINKHIP_SWEEPX_TABLE(PINKHIP_CASE)
 #undef PINKHIP_CASE
-    }
-    PH_HIP(h, ex);
-    return PINKHIP_OK;
-  }
-  if (sweep) {
-    hipError_t es = hipErrorInvalidValue;
-    switch (sc.NV * 10000 + sc.MD * 100 + sc.W) {
-#define PINKHIP_CASE(NV, MD, W)                                            \
-  case NV * 10000 + MD * 100 + W:                                          \
-    es = pinkhip::PINKHIP_LAUNCH_SWEEP_NAME(NV, MD, W)(h->stream, a);      \
-    break;
-      PINKHIP_SWEEP_TABLE(PINKHIP_CASE)
+      }
+      break;
+    case pinkhip::PLAN_SWEEP:
+      switch (p.NV * 10000 + p.MD * 100 + p.W) {
+#define PINKHIP_CASE(NV, MD, W) \
+  case NV * 10000 + MD * 100 + W: e = pinkhip::PINKHIP_LAUNCH_SWEEP_NAME(NV, MD, W)(h->stream, a); break;
+        PINKHIP_SWEEP_TABLE(PINKHIP_CASE)
 #undef PINKHIP_CASE
-    }
-    PH_HIP(h, es);
-    return PINKHIP_OK;
-  }
-  const pinkhip::PackedChoice pc = pinkhip::select_packed(a.nv, a.md);
-  static const bool force_dense = std::getenv("PINKHIP_FORCE_DENSE") != nullptr;  // development: time the dense-row instantiation on a batch without dense rows
-  hipError_t e = hipErrorInvalidValue;
-  switch (pc.NV) {
-#define PINKHIP_CASE(NV, W)                                                                   \
-  case NV:                                                                                    \
-    e = (a.md == 0 && !force_dense) ? pinkhip::PINKHIP_LAUNCH_PACKED_NAME(NV, W, 0)(h->stream, a) \
-                  : pinkhip::PINKHIP_LAUNCH_PACKED_NAME(NV, W, 1)(h->stream, a);              \
-    break;
-    PINKHIP_PACKED_TABLE(PINKHIP_CASE)
+      }
+      break;
+    case pinkhip::PLAN_SWEEP_WARM:
+      switch (p.NV * 100 + p.W) {
+#define PINKHIP_CASE(NV, MD, W) \
+  case NV * 100 + W: e = pinkhip::PINKHIP_LAUNCH_WSWEEP_NAME(NV, MD, W)(h->stream, a); break;
+        PINKHIP_WSWEEP_TABLE(PINKHIP_CASE)
 #undef PINKHIP_CASE
-    default: return fail(h, PINKHIP_E_INVALID, "unsupported nv / md");
+      }
+      break;
+    case pinkhip::PLAN_PACKED:
+      switch (p.NV) {
+#define PINKHIP_CASE(NV, W)                                                                        \
+  case NV:                                                                                         \
+    e = p.dense ? pinkhip::PINKHIP_LAUNCH_PACKED_NAME(NV, W, 1)(h->stream, a)                      \
+                : pinkhip::PINKHIP_LAUNCH_PACKED_NAME(NV, W, 0)(h->stream, a);                     \
+    break;
+        PINKHIP_PACKED_TABLE(PINKHIP_CASE)
+#undef PINKHIP_CASE
+      }
+      break;
   }
   PH_HIP(h, e);
   return PINKHIP_OK;
@@ -183,9 +177,6 @@ int prepare(pinkhip_handle *h, const pinkhip_desc *d, KernelArgs &a) {
   pinkhip::HostTables t;
   const std::string why = pinkhip::build_tables(*d, t);
   if (!why.empty()) return fail(h, PINKHIP_E_INVALID, why);
-  a.rank_deficient = pinkhip::rank_deficient_by_construction(*d) ? 1 : 0;
-  a.n_free_lead = (d->n_free_lead > 0 && d->n_free_lead <= d->nv) ? d->n_free_lead : 0;
-  a.out_scale = 1.0;
   PH_HIP(h, hipSetDevice(h->device));
 
   // pack: [row_gain K][row_lm K][barrier_safe_gain nb] doubles, then int tables
@@ -212,58 +203,13 @@ int prepare(pinkhip_handle *h, const pinkhip_desc *d, KernelArgs &a) {
     h->h_tables.swap(img);
   }
   char *dp = h->d_tables;
-  a.row_gain = reinterpret_cast<const double *>(dp);
-  a.row_lm = reinterpret_cast<const double *>(dp + 8 * K);
-  a.barrier_safe_gain = reinterpret_cast<const double *>(dp + 16 * K);
   const char *ip = dp + 8 * (2 * K + nb);
-  a.dtask_col0 = reinterpret_cast<const int *>(ip);
-  a.dtask_row0 = reinterpret_cast<const int *>(ip + 4 * nd);
-  a.dtask_k = reinterpret_cast<const int *>(ip + 8 * nd);
-  a.barrier_rows = reinterpret_cast<const int *>(ip + 12 * nd);
-
-  a.B = d->B;
-  a.nv = d->nv;
-  a.Kd = d->Kd;
-  a.K = d->K;
-  a.md = d->md;
-  a.n_eq = d->n_eq;
-  a.n_dtasks = static_cast<int>(nd);
-  a.n_barriers = static_cast<int>(nb);
-  a.cost_batched = d->cost_is_batched;
-  a.max_iter = d->max_iter;
-  a.damping = d->damping;
-  a.dt = d->dt;
+  const pinkhip::TablePtrs where{reinterpret_cast<const double *>(dp), reinterpret_cast<const double *>(dp + 8 * K),
+                                 reinterpret_cast<const double *>(dp + 16 * K), reinterpret_cast<const int *>(ip),
+                                 reinterpret_cast<const int *>(ip + 4 * nd), reinterpret_cast<const int *>(ip + 8 * nd),
+                                 reinterpret_cast<const int *>(ip + 12 * nd)};
+  pinkhip::fill_desc(*d, t, where, a);
   return PINKHIP_OK;
-}
-
-int check_problem(pinkhip_handle *h, const pinkhip_desc *d, const pinkhip_problem *in) {
-  if (!in) return fail(h, PINKHIP_E_INVALID, "null problem");
-  if (d->B == 0) return PINKHIP_OK;
-  if (d->Kd > 0 && !in->J) return fail(h, PINKHIP_E_INVALID, "J is NULL but Kd > 0");
-  if (d->K > 0 && (!in->e || !in->cost)) return fail(h, PINKHIP_E_INVALID, "e/cost NULL but K > 0");
-  if (!in->lb || !in->ub) return fail(h, PINKHIP_E_INVALID, "lb/ub must not be NULL");
-  if (d->md > 0 && (!in->Gd || !in->hd)) return fail(h, PINKHIP_E_INVALID, "Gd/hd NULL but md > 0");
-  return PINKHIP_OK;
-}
-
-void set_problem(KernelArgs &a, const pinkhip_problem *in) {
-  a.J = in->J;
-  a.e = in->e;
-  a.cost = in->cost;
-  a.lb = in->lb;
-  a.ub = in->ub;
-  a.Gd = in->Gd;
-  a.hd = in->hd;
-  a.c_extra = in->c_extra;
-}
-
-// What the warm entry points refuse beyond the validation of their cold twins (empty: nothing)
-const char *warm_refusal(const pinkhip_desc *d, const KernelArgs &a) {
-  if (d->md > 0) return "warm starts are box-only (md == 0): dense rows run the dual method, which needs a dual-feasible start";
-  if (a.rank_deficient) return "the task stack is rank deficient by construction: it is solved by the Goldfarb-Idnani kernel, which takes no active set";
-  const char *solver_env = std::getenv("PINKHIP_SOLVER");
-  if (solver_env && std::strcmp(solver_env, "packed") == 0) return "PINKHIP_SOLVER=packed: the Goldfarb-Idnani kernel takes no active set";
-  return nullptr;
 }
 
 size_t align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
@@ -423,47 +369,21 @@ int pinkhip_get_device_info(const pinkhip_handle *h, pinkhip_device_info *info) 
 int pinkhip_solve_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_problem *dev_in,
                          const pinkhip_result *dev_out) {
   KernelArgs a{};
+  std::string why;
   int rc = prepare(h, desc, a);
   if (rc) return rc;
-  if ((rc = check_problem(h, desc, dev_in))) return rc;
-  if (!dev_out || (desc->B > 0 && (!dev_out->dq || !dev_out->status)))
-    return fail(h, PINKHIP_E_INVALID, "dq/status must not be NULL");
-  set_problem(a, dev_in);
-  a.dq = dev_out->dq;
-  a.status = dev_out->status;
-  a.iters = dev_out->iters;
+  if ((rc = pinkhip::set_solve(*desc, dev_in, dev_out, false, nullptr, a, why))) return fail(h, rc, why);
   return launch(h, a, true);
 }
 
 int pinkhip_solve_warm_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_problem *dev_in,
                               const pinkhip_result *dev_out, const pinkhip_warm *warm) {
   KernelArgs a{};
+  std::string why;
   int rc = prepare(h, desc, a);
   if (rc) return rc;
-  if ((rc = check_problem(h, desc, dev_in))) return rc;
-  if (!dev_out || (desc->B > 0 && (!dev_out->dq || !dev_out->status)))
-    return fail(h, PINKHIP_E_INVALID, "dq/status must not be NULL");
-  if (!warm) return fail(h, PINKHIP_E_INVALID, "null warm-start arguments");
-  if (const char *why = warm_refusal(desc, a)) return fail(h, PINKHIP_E_UNSUPPORTED, why);
-  const pinkhip::SweepChoice sc = pinkhip::select_sweep_warm(a.nv, a.n_free_lead);
-  if (!sc.NV) return fail(h, PINKHIP_E_UNSUPPORTED, "no warm-start instantiation of the stack + solve kernel holds this nv");
-  if (a.B == 0) return PINKHIP_OK;
-  if (a.B > 0x7fffffffLL) return fail(h, PINKHIP_E_INVALID, "B exceeds the grid limit 2^31-1");
-  set_problem(a, dev_in);
-  a.dq = dev_out->dq;
-  a.status = dev_out->status;
-  a.iters = dev_out->iters;
-  a.active_in = warm->active_in;
-  a.active_out = warm->active_out;
-  hipError_t e = hipErrorInvalidValue;
-  switch (sc.NV * 100 + sc.W) {
-#define PINKHIP_CASE(NV, MD, W) \
-  case NV * 100 + W: e = pinkhip::PINKHIP_LAUNCH_WSWEEP_NAME(NV, MD, W)(h->stream, a); break;
-    PINKHIP_WSWEEP_TABLE(PINKHIP_CASE)
-#undef PINKHIP_CASE
-  }
-  PH_HIP(h, e);
-  return PINKHIP_OK;
+  if ((rc = pinkhip::set_solve(*desc, dev_in, dev_out, true, warm, a, why))) return fail(h, rc, why);
+  return launch(h, a, true, true);
 }
 
 int pinkhip_stack_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_problem *dev_in,
@@ -471,9 +391,9 @@ int pinkhip_stack_device(pinkhip_handle *h, const pinkhip_desc *desc, const pink
   KernelArgs a{};
   int rc = prepare(h, desc, a);
   if (rc) return rc;
-  if ((rc = check_problem(h, desc, dev_in))) return rc;
+  if (const char *bad = pinkhip::problem_fault(*desc, dev_in)) return fail(h, PINKHIP_E_INVALID, bad);
   if (desc->B > 0 && (!H_out || !c_out)) return fail(h, PINKHIP_E_INVALID, "H_out/c_out must not be NULL");
-  set_problem(a, dev_in);
+  pinkhip::set_problem(a, *dev_in);
   a.H_out = H_out;
   a.c_out = c_out;
   return launch(h, a, false);
@@ -508,11 +428,10 @@ ArenaPlan plan_arena(const pinkhip_desc *d, const pinkhip_problem *in, size_t ex
 int pinkhip_solve_host(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_problem *host_in,
                        const pinkhip_result *host_out) {
   KernelArgs a{};
+  std::string why;
   int rc = prepare(h, desc, a);
   if (rc) return rc;
-  if ((rc = check_problem(h, desc, host_in))) return rc;
-  if (!host_out || (desc->B > 0 && (!host_out->dq || !host_out->status)))
-    return fail(h, PINKHIP_E_INVALID, "dq/status must not be NULL");
+  if ((rc = pinkhip::set_solve(*desc, host_in, host_out, false, nullptr, a, why))) return fail(h, rc, why);  // (validated; the streams are staged below)
   if (desc->B == 0) return PINKHIP_OK;
   const size_t B = static_cast<size_t>(desc->B), nv = desc->nv;
   const size_t n_dq = align256(8 * B * nv), n_st = align256(4 * B);
@@ -617,7 +536,7 @@ int pinkhip_stack_host(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhi
   KernelArgs a{};
   int rc = prepare(h, desc, a);
   if (rc) return rc;
-  if ((rc = check_problem(h, desc, host_in))) return rc;
+  if (const char *bad = pinkhip::problem_fault(*desc, host_in)) return fail(h, PINKHIP_E_INVALID, bad);
   if (desc->B == 0) return PINKHIP_OK;
   if (!H_out || !c_out) return fail(h, PINKHIP_E_INVALID, "H_out/c_out must not be NULL");
   const size_t B = static_cast<size_t>(desc->B), nv = desc->nv;
@@ -625,7 +544,7 @@ int pinkhip_stack_host(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhi
   pinkhip_problem dev{};
   char *out = nullptr;
   if ((rc = upload(h, desc, host_in, n_H + n_c, dev, out))) return rc;
-  set_problem(a, &dev);
+  pinkhip::set_problem(a, dev);
   a.H_out = reinterpret_cast<double *>(out);
   a.c_out = reinterpret_cast<double *>(out + n_H);
   if ((rc = launch(h, a, false))) return rc;
@@ -638,25 +557,7 @@ int pinkhip_stack_host(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhi
 int pinkhip_frame_task_device(pinkhip_handle *h, int64_t B, int32_t nv, const double *T_frame,
                               const double *T_target, const double *J_body, double *e_out,
                               double *J_out) {
-  if (!h) return fail(nullptr, PINKHIP_E_INVALID, "null handle");
-  if (B < 0 || nv < 1 || nv > PINKHIP_MAX_NV) return fail(h, PINKHIP_E_INVALID, "bad B / nv");
-  if (B == 0) return PINKHIP_OK;
-  if (!T_frame || !T_target || !J_body || !e_out || !J_out) return fail(h, PINKHIP_E_INVALID, "null pointer");
-  if (B > 0x7fffffffLL) return fail(h, PINKHIP_E_INVALID, "B exceeds the grid limit");
-  PH_HIP(h, hipSetDevice(h->device));
-  pinkhip::FrameTaskArgs a{B, nv, T_frame, T_target, J_body, e_out, J_out};
-  const dim3 block(pinkhip::kWave);
-  if (nv <= 8) {
-    hipLaunchKernelGGL(pinkhip::ik_frame_task_kernel<8>, dim3((unsigned)((B + 7) / 8)), block, 0, h->stream, a);
-  } else if (nv <= 16) {
-    hipLaunchKernelGGL(pinkhip::ik_frame_task_kernel<16>, dim3((unsigned)((B + 3) / 4)), block, 0, h->stream, a);
-  } else if (nv <= 32) {
-    hipLaunchKernelGGL(pinkhip::ik_frame_task_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 0, h->stream, a);
-  } else {
-    hipLaunchKernelGGL(pinkhip::ik_frame_task_kernel<64>, dim3((unsigned)B), block, 0, h->stream, a);
-  }
-  PH_HIP(h, hipGetLastError());
-  return PINKHIP_OK;
+  return pinkhip_frame_task_strided_device(h, B, nv, T_frame, 0, T_target, 0, J_body, 0, e_out, 0, J_out, 0);  // (0: densely packed)
 }
 
 int pinkhip_frame_task_host(pinkhip_handle *h, int64_t B, int32_t nv, const double *T_frame,
@@ -807,25 +708,7 @@ int pinkhip_step_device(pinkhip_handle *h, const pinkhip_model *m, int64_t B, co
   if (!(st->dt > 0.0) || !(st->config_limit_gain > 0.0 && st->config_limit_gain <= 1.0)) return fail(h, PINKHIP_E_INVALID, "bad dt / gain");
   if (st->step < 0 || st->step >= (1 << 23)) return fail(h, PINKHIP_E_INVALID, "bad step");
   PH_HIP(h, hipSetDevice(h->device));
-  pinkhip::FkArgs a{m->dev, B, st->q, st->T_frames, nullptr};
-  a.T_target = st->T_target;
-  a.e_out = st->e;
-  a.J_out = st->J;
-  a.sE = st->sE;
-  a.sJo = st->sJ;
-  a.q_rw = st->q;
-  a.dq_prev = st->dq_prev;
-  a.status = st->status;
-  a.first_failure = st->first_failure;
-  a.step = st->step;
-  a.dt = st->dt;
-  a.config_limit_gain = st->config_limit_gain;
-  a.root_box = st->root_box;
-  a.q_target = st->q_target;
-  a.target_batched = st->target_batched;
-  a.lb = st->lb;
-  a.ub = st->ub;
-  a.e_off = st->e_off;
+  const pinkhip::FkArgs a = pinkhip::step_args(m->dev, B, *st);
   const int per = pinkhip::fk_lds_doubles(m->dev.nj, m->dev.nf);
   const dim3 block(pinkhip::kWave);
   const int width = m->dev.nv > m->dev.nj ? m->dev.nv : m->dev.nj;
@@ -847,112 +730,27 @@ static int rollout_step_launch(pinkhip_handle *h, const pinkhip_desc *desc, cons
   pinkhip::RolloutArgs ra{};
   int rc = prepare(h, desc, ra.k);
   if (rc) return rc;
-  if (warm) {
-    if (const char *why = warm_refusal(desc, ra.k)) return fail(h, PINKHIP_E_UNSUPPORTED, why);
-    ra.k.active_in = warm->active_in;
-    ra.k.active_out = warm->active_out;
-  }
-  const pinkhip::ModelDev &md = m->dev;
-  if (desc->B == 0) return PINKHIP_OK;
-  const int n_crow = st->n_const_rows;
-  if (n_crow < 0 || (n_crow > 0 && (!st->const_rows || !st->const_q0 || !st->const_b)))
-    return fail(h, PINKHIP_E_INVALID, "n_const_rows must be >= 0 and come with const_rows / const_q0 / const_b");
-  const int n_eqf = st->n_constraint_frames;
-  if (n_eqf < 0 || n_eqf > pinkhip::kRolloutMaxEqFrames || (n_eqf > 0 && (!st->constraint_frame || !st->constraint_gain)))
-    return fail(h, PINKHIP_E_INVALID, "n_constraint_frames must lie in [0, 2] and come with constraint_frame / constraint_gain");
-  if (desc->nv != md.nv || desc->n_eq != 6 * n_eqf)
-    return fail(h, PINKHIP_E_INVALID, "descriptor does not describe this model's task stack (nv, n_eq = 6 n_constraint_frames)");
-  if (st->n_limit_rows < 0 || 6 * n_eqf + st->n_limit_rows > desc->md || (st->n_limit_rows > 0 && (!st->limit_rows || !st->limit_h)))
-    return fail(h, PINKHIP_E_INVALID, "n_limit_rows must lie in [0, md - n_eq] and come with limit_rows / limit_h");
-  if (desc->md > 6 * n_eqf + st->n_limit_rows &&
-      (!st->barrier_frame || !st->barrier_axis || !st->barrier_sign || !st->barrier_bound || !st->barrier_gain || !st->barrier_frame2))
-    return fail(h, PINKHIP_E_INVALID, "barrier rows need the barrier_* tables, barrier_frame2 included (-1 for the rows of a position barrier)");
-  if ((st->root_box || st->n_limit_rows) && md.root_nv != 6)
-    return fail(h, PINKHIP_E_INVALID, "a floating-base velocity limit needs a free-flyer root joint");
-  int post_row0 = 0, post_k = 0;
-  {
-    const std::string why = pinkhip::rollout_task_layout(*desc, md.nf, md.nv, md.root_nv, n_crow, st->posture_task, st->diag_error != nullptr, post_row0, post_k);
-    if (!why.empty()) return fail(h, PINKHIP_E_INVALID, why);
-  }
-  const int n_post = post_k;
-  if (!st->q || !st->cost || !st->dq || !st->status || (md.nf > 0 && !st->T_target) || (n_post && !st->q_target))
-    return fail(h, PINKHIP_E_INVALID, "null pointer");
-  if (!(st->config_limit_gain > 0.0 && st->config_limit_gain <= 1.0) || st->step < 0 || st->step >= (1 << 23))
-    return fail(h, PINKHIP_E_INVALID, "bad limit gain / step");
-  const int fkd = pinkhip::rollout_fk_doubles(md.nj, md.nf, n_crow);
-  ra.n_crow = n_crow;
-  ra.crow_A = st->const_rows;
-  ra.crow_q0 = st->const_q0;
-  ra.crow_b = st->const_b;
-  ra.post_row0 = post_row0;
-  ra.post_k = post_k;
-  ra.diag_e = st->diag_error;
-  pinkhip::PackedChoice pc{0, 0};
-  pinkhip::SweepChoice dc{0, 0, 0};
-  if (desc->md > 0) {
-    dc = pinkhip::select_rollout_dense(md.nv, md.nj, fkd, desc->md, md.nf, n_eqf);
-    if (dc.NV == 0 || md.nf > 32) return fail(h, PINKHIP_E_UNSUPPORTED, "no whole-step instantiation with barrier rows fits this model");
-    ra.k.lds_pitch = pinkhip::rollout_lds_doubles(dc.NV, dc.W, fkd, dc.MD, md.nf, n_eqf);
-    ra.bar_frame = st->barrier_frame;
-    ra.bar_axis = st->barrier_axis;
-    ra.bar_sign = st->barrier_sign;
-    ra.bar_bound = st->barrier_bound;
-    ra.bar_gain = st->barrier_gain;
-    ra.n_lim = st->n_limit_rows;
-    ra.lim_rows = st->limit_rows;
-    ra.lim_h = st->limit_h;
-    ra.n_eqf = n_eqf;
-    ra.eq_frame = st->constraint_frame;
-    ra.eq_gain = st->constraint_gain;
-    ra.bar_frame2 = st->barrier_frame2;
-  } else {
-    pc = warm ? pinkhip::select_rollout_warm(md.nv, md.nj, fkd)
-              : pinkhip::select_rollout(md.nv, md.nj, fkd, st->n_const_rows > 0 || st->diag_error != nullptr || st->acc_limit != nullptr || m->image.has_relative);
-    if (pc.NV == 0 || md.nf > 32) return fail(h, PINKHIP_E_UNSUPPORTED, "no whole-step instantiation fits this model");
-    ra.k.lds_pitch = pinkhip::rollout_lds_doubles(pc.NV, pc.W, fkd);
-  }
-  ra.k.cost = st->cost;
-  ra.k.out_scale = (st->dq_scale != 0.0) ? st->dq_scale : 1.0;
-  if (st->dq_scale != 0.0 && st->dq_scale != 1.0 && st->integrate)
-    return fail(h, PINKHIP_E_INVALID, "dq_scale rescales what is written to dq: not together with integrate (the next step reads dq)");
-  ra.k.dq = st->dq;
-  ra.k.status = st->status;
-  ra.k.iters = st->iters;
-  pinkhip::FkArgs &f = ra.fk;
-  f.m = md;
-  f.B = desc->B;
-  f.q = st->q;
-  f.q_rw = st->q;
-  f.T_frames = st->T_frames;
-  f.T_target = st->T_target;
-  f.sTb = st->sT_b;
-  f.sTf = (st->sT_b || st->sT_f) ? st->sT_f : 12;
-  f.dt = desc->dt;
-  f.config_limit_gain = st->config_limit_gain;
-  f.root_box = st->root_box;
-  f.acc_limit = st->acc_limit;
-  f.q_target = n_post ? st->q_target : nullptr;
-  f.target_batched = st->target_batched;
-  ra.integrate = st->integrate;
-  ra.first_failure = st->first_failure;
-  ra.step = st->step;
+  LaunchPlan p;
+  std::string why;
+  if ((rc = pinkhip::plan_rollout(*desc, m->dev, m->image.has_relative, *st, warm, std::getenv("PINKHIP_SOLVER"), ra, p, why))) return fail(h, rc, why);
+  if (p.kind == pinkhip::PLAN_NONE) return PINKHIP_OK;
   hipError_t e = hipErrorInvalidValue;
-  if (desc->md > 0) {
-    switch (dc.NV * 100 + dc.MD) {
+  if (p.kind == pinkhip::PLAN_ROLLOUT_DENSE) {
+    switch (p.NV * 100 + p.MD) {
 #define PINKHIP_CASE(NV, MD, W) \
   case NV * 100 + MD: e = pinkhip::PINKHIP_LAUNCH_ROLLOUT_DENSE_NAME(NV, MD, W)(h->stream, ra); break;
       PINKHIP_ROLLOUT_DENSE_TABLE(PINKHIP_CASE)
 #undef PINKHIP_CASE
     }
-  } else if (warm) {
-    switch (pc.NV) {
+  } else if (p.kind == pinkhip::PLAN_ROLLOUT_WARM) {
+    switch (p.NV) {
 #define PINKHIP_CASE(NV, W) \
   case NV: e = pinkhip::PINKHIP_LAUNCH_WROLLOUT_NAME(NV, W)(h->stream, ra); break;
       PINKHIP_WROLLOUT_TABLE(PINKHIP_CASE)
 #undef PINKHIP_CASE
     }
   } else {
-    switch (pc.NV) {
+    switch (p.NV) {
 #define PINKHIP_CASE(NV, W) \
   case NV: e = pinkhip::PINKHIP_LAUNCH_ROLLOUT_NAME(NV, W)(h->stream, ra); break;
       PINKHIP_ROLLOUT_TABLE(PINKHIP_CASE)

@@ -1,13 +1,10 @@
 // Warm-start twins of the tableau kernels under the CPU wave emulator -- TEST INFRASTRUCTURE ONLY (see wave_emu.h).
-// Additive to emu_lanes.h / emu_registry.h: two registry kinds of their own and the per-lane entry points of
-// ik_solve_sweep_warm_kernel / ik_rollout_warm_kernel (tu_wsweep.hip / tu_wrollout.hip).
+// The per-lane entry points of ik_solve_sweep_warm_kernel / ik_rollout_warm_kernel (tu_wsweep.hip / tu_wrollout.hip),
+// registered by emu_warm_part.cpp under KIND_SWEEP_WARM / KIND_ROLLOUT_WARM of emu_registry.h.
 #pragma once
 #include "emu_lanes.h"
 
 namespace pinkemu {
-
-// (behind the kinds of emu_registry.h: the registry is keyed by plain integers)
-constexpr int KIND_SWEEP_WARM = 100, KIND_ROLLOUT_WARM = 101;
 
 template <int NV, int MD, int W>
 void lane_main_sweep_warm(void *p) {

@@ -71,6 +71,19 @@ def test_descriptor_validation(emu):
         assert rc == -1 and re.search(word, msg), (rc, msg)
 
 
+def test_host_plan_invariants(tmp_path):
+    """tests/emu/host_plan_check.cpp, built with the address and undefined-behaviour sanitizers and run as a child process:
+    whatever host_plan.h plans for nv = 1..64 x md x n_free_lead x B x PINKHIP_SOLVER, cold and warm, and for the whole-step
+    kernel, holds the problem, covers B, is an entry of its X-macro table and fits the LDS; the warm refusals are refused."""
+    import subprocess
+
+    exe = str(tmp_path / "host_plan_check")
+    subprocess.run(["g++", "-std=c++17", "-Wno-psabi", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    os.path.join(ROOT, "tests", "emu", "host_plan_check.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "checks passed" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+
+
 def test_makefile_builds_every_instantiation_of_the_dispatch_table():
     """dispatch.h (PINKHIP_PACKED_TABLE) is the single source of the (NV, W) instantiations; the Makefile has to
     compile one translation unit per entry (x DENSE in {0, 1}) or the link fails only on the GPU box."""

@@ -273,39 +273,36 @@ def test_whole_step_kernel_bands(solver, md):
     assert not len(bad), [(rec["tag"][i], float(rec["kappa"][i]), int(rec["path"][i]), float(rec["err"][i]), float(rec["err_oracle"][i])) for i in bad[:8]]
 
 
-def _dispatch_table(name):
-    """The (NV, MD, W) entries of a table macro of pink_amd/csrc/dispatch.h (the release definition, not the development one)."""
-    import os
-    import re
-
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pink_amd", "csrc", "dispatch.h")).read()
-    src = src.replace("\\\n", " ")
-    for line in src.splitlines():
-        found = [tuple(int(v) for v in m) for m in re.findall(r"X\((\d+), (\d+), (\d+)\)", line)]
-        if line.startswith(f"#define {name}(X)") and "PINKHIP_DEV" not in line and found:  # (the empty definitions are development-only)
-            return found
-    raise AssertionError(name)
-
-
-def test_banded_families_reach_their_instantiations():
-    """Each family of the bands reaches the instantiation kind it stands for, by dispatch.h's own rules (select_sweep,
-    select_sweepx, prefer_sweepx restated over the tables parsed from the header): box-only <NV,0,W> one lane per
+def test_banded_families_reach_their_instantiations(emu, monkeypatch):
+    """Each family of the bands reaches the instantiation kind it stands for, by the plan the library itself runs
+    (pink_amd/csrc/host_plan.h, asked through the emulator's pinkhip_emu_plan_solve): box-only <NV,0,W> one lane per
     coordinate, eliminating <34,0,32>, dense rows <NV,MD,W> with MD > 0 and not the virtual-row kernel, virtual dense
-    rows ik_sweepx.h.  An edit of the tables that moves a family to another kernel fails here."""
-    sweep, sweepx = _dispatch_table("PINKHIP_SWEEP_TABLE"), _dispatch_table("PINKHIP_SWEEPX_TABLE")
+    rows ik_sweepx.h.  An edit of the tables or of the rule that moves a family to another kernel fails here."""
+    import ctypes
 
-    def select_sweep(nv, md, lead=0):
-        for NV, MD, W in sweep:
-            if nv <= NV and md <= MD and (md > 0) == (MD > 0) and (NV <= W or lead >= NV - W):
-                return NV, MD, W
-        return None
+    from pink_amd._lib import Desc
 
-    def select_sweepx(nv, md):
-        return next(((NV, MD, W) for NV, MD, W in sweepx if md > 0 and nv <= NV and md <= MD), None)
+    PLAN_SWEEP, PLAN_SWEEPX = 3, 4  # host_plan.h PlanKind
+    emu.lib.pinkhip_emu_plan_solve.argtypes = [ctypes.POINTER(Desc), ctypes.POINTER(ctypes.c_int * 6)]
 
-    def prefer_sweepx(nv, md):
-        x, s_ = select_sweepx(nv, md), select_sweep(nv, md)
-        return x is not None and (s_ is None or x[2] < s_[2])
+    def plan(nv, md, lead, solver):
+        """(kind, NV, MD, W) for a batch of full rank with md dense rows under PINKHIP_SOLVER = solver (None: unset)"""
+        if solver is None:
+            monkeypatch.delenv("PINKHIP_SOLVER", raising=False)
+        else:
+            monkeypatch.setenv("PINKHIP_SOLVER", solver)
+        d = Desc(B=256, nv=nv, md=md, damping=1e-3, dt=0.01, max_iter=100, n_free_lead=lead)
+        out = (ctypes.c_int * 6)()
+        rc = emu.lib.pinkhip_emu_plan_solve(ctypes.byref(d), ctypes.byref(out))
+        assert rc == 0, (rc, emu.lib.pinkhip_emu_last_error().decode())
+        return tuple(out[:4])
+
+    def select_sweep(nv, md, lead=0):  # the tableau instantiation with one lane per row that holds the problem, if any
+        p = plan(nv, md, lead, "sweep")
+        return p[1:] if p[0] == PLAN_SWEEP else None
+
+    def prefer_sweepx(nv, md):  # is the kernel with virtual dense rows the one that runs it?
+        return plan(nv, md, 0, None)[0] == PLAN_SWEEPX
 
     for fam, shapes in ps.BANDED_FAMILIES.items():
         for nv, md, neq, lead in shapes:
