@@ -32,6 +32,8 @@
 #define PINKHIP_OCCUPANCY_FK
 #define PINKHIP_OCCUPANCY_SMALL_STACK
 
+#include "../../pink_amd/csrc/fast_sincos.h"  // rint + fma only: the emulator runs the device's sin / cos arithmetic
+
 // element-wise kernels use blockIdx / threadIdx directly; the emulator calls their per-thread
 // bodies in a plain loop and only needs the names to exist
 struct EmuDim3 {
@@ -186,10 +188,7 @@ inline int key_payload(double k) {
   std::memcpy(&b, &k, 8);
   return (int)(b & 0xFF);
 }
-inline void fast_sincos(double t, double &sn, double &cs) {
-  sn = std::sin(t);
-  cs = std::cos(t);
-}
+// (fast_sincos: the device's own reduction and polynomials, ../../pink_amd/csrc/fast_sincos.h, included above)
 inline double fast_rcp(double x) { return 1.0 / x; }
 inline double fast_rsqrt(double x) { return 1.0 / std::sqrt(x); }
 inline double fast_rcp1(double x) { return 1.0 / x; }

@@ -29,6 +29,60 @@ def _models():
     return [(arm, ["tool0"]), (humanoid, ["tool0", "mid"]), (arm12, ["tool0", "joint_6"]), (big, ["tool0", "joint_12"])]
 
 
+def _edge_models():
+    """Trees with PRISMATIC joints at the joint counts of ``_models()`` (the same kernel instantiations): the
+    ``angular`` / ``lin`` branch of the Jacobian columns, ``joint_transform``'s translation and the whole-step kernel's
+    sink run with a joint type that ``build_chain`` never makes.  Generic unit axes, rotated placements.
+      tree15   free-flyer + 9 joints, every third one prismatic; two branches of different depth leave joint_3 (pointer
+               jumping sees unequal depths); frames on both tips and mid-chain
+      arm12p   12 joints, four prismatic (the 16-lane group)
+      big30p   free-flyer + 24 joints, four prismatic (the 32-lane group)
+    Limits leave room around the start configurations of the loops below (|q| <= 0.6 on a revolute, 0.3 on a
+    prismatic joint)."""
+
+    def add(model, i, parent, rng, prismatic):
+        off = SE3(exp3(0.4 * rng.normal(size=3)), [0.2 + 0.1 * (i % 2), 0.03 * (i % 3 - 1), 0.05 * (i % 3)])
+        if prismatic:
+            return model.add_joint(f"joint_{i}", "prismatic", parent, off, rng.normal(size=3), -0.8, 0.8, 1.0)
+        return model.add_joint(f"joint_{i}", "revolute", parent, off, rng.normal(size=3), -np.pi, np.pi, 3.15)
+
+    tip = SE3(exp3([0.2, -0.1, 0.3]), [0.15, 0.02, -0.04])
+    rng = np.random.default_rng(21)
+    tree = pink_amd.configuration.Model()
+    p = tree.add_joint("root_joint", "free_flyer")
+    for i in (1, 2, 3):
+        p = add(tree, i, p, rng, i % 3 == 0)
+    fork = p
+    for i in (4, 5, 6, 7):  # the long branch
+        p = add(tree, i, p, rng, i % 3 == 0)
+    tree.add_frame("tip_a", p, tip)
+    p = fork
+    for i in (8, 9):  # the short one
+        p = add(tree, i, p, rng, i % 3 == 0)
+    tree.add_frame("tip_b", p, tip)
+
+    rng = np.random.default_rng(22)
+    arm = pink_amd.configuration.Model()
+    p = -1
+    for i in range(1, 13):
+        p = add(arm, i, p, rng, i % 3 == 0)
+    arm.add_frame("tool0", p, tip)
+
+    rng = np.random.default_rng(23)
+    big = pink_amd.configuration.Model()
+    p = big.add_joint("root_joint", "free_flyer")
+    for i in range(1, 25):
+        p = add(big, i, p, rng, i % 6 == 0)
+    big.add_frame("tool0", p, tip)
+    return {"tree15": (tree, ["tip_a", "tip_b", "joint_2"]), "arm12p": (arm, ["tool0", "joint_6"]),
+            "big30p": (big, ["tool0", "joint_12"])}
+
+
+def _pick(which):
+    """``_models()[which]`` for an index, ``_edge_models()[which]`` for a name."""
+    return _edge_models()[which] if isinstance(which, str) else _models()[which]
+
+
 def _random_q(model, B, rng):
     q = np.tile(model.neutral(), (B, 1))
     for j in model.joints:
@@ -138,15 +192,16 @@ def test_fk_and_integrate_against_the_independent_oracle(api):
 
 
 @pytest.mark.parametrize("fused", [True, "kernel"])
-@pytest.mark.parametrize("which", [0, 1])
+@pytest.mark.parametrize("which", [0, 1, "tree15", "arm12p", "big30p"])
 def test_closed_loop_matches_host_loop_and_converges(api, which, fused):
     """tests/test_solve_ik.py:160-210 / examples/inverse_kinematics_ur10.py:75-91, batched; with two launches per
-    step (step kernel + solve) and with the whole step in one kernel."""
-    model, frames = _models()[which]
-    rng = np.random.default_rng(10 + which)
-    B, dt, steps = 4, 5e-3, 40
+    step (step kernel + solve) and with the whole step in one kernel.  The named models (``_edge_models``) carry
+    prismatic joints."""
+    model, frames = _pick(which)
+    rng = np.random.default_rng(10 + (which if isinstance(which, int) else len(which) + model.nv))
+    B, dt, steps = 4, 5e-3, (40 if isinstance(which, int) else 12)
     q0 = _random_q(model, B, rng) * 0.5 + 0.5 * np.tile(model.neutral(), (B, 1))
-    if which == 1:
+    if model.root_joint is not None:
         q0[:, 3:7] /= np.linalg.norm(q0[:, 3:7], axis=1, keepdims=True)
     cfgs = [Configuration(model, q0[b]) for b in range(B)]
     specs = [(f, 1.0, 0.5 if i == 0 else 0.0, 1.0, 1e-3) for i, f in enumerate(frames)]
@@ -168,7 +223,7 @@ def test_closed_loop_matches_host_loop_and_converges(api, which, fused):
     ro.set_targets(targets)
     ro.run(steps)
     # the one-kernel step exists for the floating-base model; the 6-dof arm (an 8-lane group) keeps two launches
-    assert ro.fused == (fused if which == 1 else True)
+    assert ro.fused == (fused if which != 0 else True)
     qd = ro.configurations()
     _, st, _ = ro.last_step()
     assert (st == 0).all()
@@ -185,18 +240,20 @@ def test_closed_loop_matches_host_loop_and_converges(api, which, fused):
     ro.free()
 
 
-@pytest.mark.parametrize("which", [1, 2, 3])
+@pytest.mark.parametrize("which", [1, 2, 3, "tree15", "arm12p", "big30p"])
 def test_closed_loop_with_position_barriers_matches_host_loop(api, which):
     """PositionBarrier rows (pink/barriers/position_barrier.py:109-153; G = -J_h / dt, h = gain * barrier,
     pink/barriers/barrier.py:246-254) formed on chip by the whole-step kernel: the closed loop with two barriers --
     one of them active along the way, one with a safe-displacement gain -- follows the host loop (per-instance
-    solve_ik(..., barriers=...) + integrate_inplace) to 1e-8, and solve_ik_batch takes the same device path."""
+    solve_ik(..., barriers=...) + integrate_inplace) to 1e-8, and solve_ik_batch takes the same device path.  On the
+    named models (``_edge_models``) both barrier frames sit behind prismatic joints."""
     from pink_amd import solve_ik_batch
     from pink_amd.barriers import PositionBarrier
 
-    model, frames = _models()[which]
-    rng = np.random.default_rng(70 + which)
-    B, dt, steps = 3, 5e-3, (25 if which != 3 else 12)
+    model, frames = _pick(which)
+    frames = frames[:2]
+    rng = np.random.default_rng(70 + (which if isinstance(which, int) else len(which) + model.nv))
+    B, dt, steps = 3, 5e-3, (25 if which in (1, 2) else 12)
     q0 = _random_q(model, B, rng) * 0.5 + 0.5 * np.tile(model.neutral(), (B, 1))
     if model.root_joint is not None:
         q0[:, 3:7] /= np.linalg.norm(q0[:, 3:7], axis=1, keepdims=True)
@@ -425,16 +482,17 @@ def test_failed_solves_are_not_integrated_and_stay_visible(api, mode):
     assert lim.value.instance == 2 and lim.value.joint == j
 
 
-@pytest.mark.parametrize("which", [0, 1, 2])
+@pytest.mark.parametrize("which", [0, 1, 2, "tree15", "arm12p", "big30p"])
 def test_one_kernel_step_equals_two_launch_step(api, which):
     """pinkhip_rollout_step_device forms the task rows on chip (world twists x per-frame blocks) instead of reading
     them from HBM: after every step dq, status and the configurations must agree with the step-kernel + solve loop
-    to round-off (the rows are the same numbers computed in a different order)."""
-    model, frames = _models()[which]
-    rng = np.random.default_rng(50 + which)
+    to round-off (the rows are the same numbers computed in a different order).  The named models (``_edge_models``)
+    carry prismatic joints: their columns' world twists go through the kernel's sink as [u; 0]."""
+    model, frames = _pick(which)
+    rng = np.random.default_rng(50 + (which if isinstance(which, int) else len(which) + model.nv))
     B = 5
     q0 = _random_q(model, B, rng) * 0.6 + 0.4 * np.tile(model.neutral(), (B, 1))
-    if which == 1:
+    if model.root_joint is not None:
         q0[:, 3:7] /= np.linalg.norm(q0[:, 3:7], axis=1, keepdims=True)
     specs = [(f, 1.0, 0.5, 0.9, 1e-3) for f in frames]
     targets = np.zeros((B, len(frames), 12))
@@ -452,7 +510,7 @@ def test_one_kernel_step_equals_two_launch_step(api, which):
             api.sync()
             dq, st, it = ro.last_step()
             hist.append((dq.copy(), st.copy(), ro.configurations().copy()))
-        assert ro.fused == (mode if which >= 1 else True)
+        assert ro.fused == (mode if which != 0 else True)
         runs[mode] = hist
         ro.free()
     for (dq_a, st_a, q_a), (dq_b, st_b, q_b) in zip(runs[True], runs["kernel"]):
