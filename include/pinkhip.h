@@ -399,6 +399,38 @@ int pinkhip_solve_warm_device(pinkhip_handle *h, const pinkhip_desc *desc, const
 int pinkhip_rollout_step_warm_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_model *model,
                                      const pinkhip_rollout_step *args, const pinkhip_warm *warm);
 
+/* ---- SelfCollisionBarrier rows of sphere pairs, selected and formed by the whole-step kernel ----
+ * Spheres are rigidly attached to joints (centre in the joint frame, radius); a pair names two spheres.  Per robot and
+ * step the kernel computes the world centres, the distance dist_k = |c_b - c_a| - r_a - r_b of every pair, keeps the
+ * n_rows pairs with the smallest distance (ascending, ties to the lower pair index) and forms one dense row per kept
+ * pair (pink/barriers/self_collision_barrier.py:85-224, barrier.py:193-254, identity class-K function):
+ *     G = -J / dt,  J_i = n . (v_i(c_a) - v_i(c_b)),  h = gain (dist - d_min),
+ * n the unit vector from the nearest point of b to that of a, v_i(c) the world velocity of the centre per unit velocity
+ * of tangent column i (zero unless column_mask says the column moves the sphere).  A pair whose nearest points
+ * coincide to np.allclose's tolerances gets a zero row, as in the reference.
+ *
+ * The rows are the LAST n_rows of desc.md and the last group of desc.barrier_rows (its barrier_safe_gain entry is the
+ * barrier's).  The barrier_* tables of the step describe the barrier rows in FRONT of them
+ * (md - n_eq - n_limit_rows - n_rows entries; may be NULL when there are none).
+ *
+ * Refused, having touched nothing: PINKHIP_E_UNSUPPORTED for more than 32 spheres, more than 64 pairs, or when no
+ * instantiation fits the model; PINKHIP_E_INVALID for n_rows outside [1, n_pairs], a NULL table, or rows that are not
+ * the last barrier group.  The caller guarantees sphere_joint < nj and pair_sphere < n_spheres (device tables). */
+#define PINKHIP_HAS_SPHERE_PAIRS 1
+typedef struct pinkhip_sphere_pairs {
+  int32_t n_spheres;           /* <= 32 */
+  const int32_t *sphere_joint; /* [n_spheres] device */
+  const double *sphere_centre; /* [n_spheres,3] device, joint frame */
+  const double *sphere_radius; /* [n_spheres] device */
+  const uint32_t *column_mask; /* [nv] device: bit s = the joint of tangent column i is sphere s's joint or an ancestor of it */
+  int32_t n_pairs;             /* <= 64 */
+  const int32_t *pair_sphere;  /* [n_pairs,2] device */
+  int32_t n_rows;              /* the LAST n_rows of desc.md; the last group of desc.barrier_rows */
+  double d_min, gain;
+} pinkhip_sphere_pairs;
+int pinkhip_rollout_step_pairs_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_model *model,
+                                      const pinkhip_rollout_step *args, const pinkhip_sphere_pairs *pairs);
+
 /* q [B,nq], q_target [nq] or [B,nq] -> lb, ub [B,nv]; posture error written into e [B,K] at columns
  * e_off .. e_off + nv - root_nv (e may be NULL) */
 int pinkhip_limits_posture_device(pinkhip_handle *h, const pinkhip_model *model, int64_t B, double dt,

@@ -124,6 +124,17 @@ class Warm(ctypes.Structure):
     _fields_ = [("active_in", ctypes.c_void_p), ("active_out", ctypes.c_void_p)]
 
 
+class SpherePairsArgs(ctypes.Structure):
+    """``pinkhip_sphere_pairs``: spheres attached to joints, the pairs among them and which dense rows they form."""
+
+    _fields_ = [
+        ("n_spheres", ctypes.c_int32), ("sphere_joint", ctypes.c_void_p), ("sphere_centre", ctypes.c_void_p),
+        ("sphere_radius", ctypes.c_void_p), ("column_mask", ctypes.c_void_p),
+        ("n_pairs", ctypes.c_int32), ("pair_sphere", ctypes.c_void_p), ("n_rows", ctypes.c_int32),
+        ("d_min", ctypes.c_double), ("gain", ctypes.c_double),
+    ]
+
+
 # every symbol include/pinkhip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "pinkhip_version", "pinkhip_device_count", "pinkhip_create", "pinkhip_destroy",
@@ -133,6 +144,7 @@ ABI_SYMBOLS = (
     "pinkhip_fk_frame_tasks_device", "pinkhip_step_device", "pinkhip_rollout_step_device",
     "pinkhip_limits_posture_device", "pinkhip_check_limits_device", "pinkhip_integrate_device", "pinkhip_integrate_checked_device",
     "pinkhip_pose_targets_device", "pinkhip_solve_warm_device", "pinkhip_rollout_step_warm_device",
+    "pinkhip_rollout_step_pairs_device",
     "pinkhip_comm_get_unique_id", "pinkhip_comm_init", "pinkhip_comm_gather", "pinkhip_comm_gather_bytes",
     "pinkhip_comm_allgather_bytes", "pinkhip_comm_destroy",
     "pinkhip_host_alloc", "pinkhip_host_free", "pinkhip_malloc", "pinkhip_free",
@@ -180,6 +192,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.pinkhip_rollout_step_device.argtypes = [vp, ctypes.POINTER(Desc), vp, ctypes.POINTER(RolloutStep)]
     lib.pinkhip_solve_warm_device.argtypes = [vp, ctypes.POINTER(Desc), ctypes.POINTER(Problem), ctypes.POINTER(Result), ctypes.POINTER(Warm)]
     lib.pinkhip_rollout_step_warm_device.argtypes = [vp, ctypes.POINTER(Desc), vp, ctypes.POINTER(RolloutStep), ctypes.POINTER(Warm)]
+    lib.pinkhip_rollout_step_pairs_device.argtypes = [vp, ctypes.POINTER(Desc), vp, ctypes.POINTER(RolloutStep), ctypes.POINTER(SpherePairsArgs)]
     lib.pinkhip_limits_posture_device.argtypes = [vp, vp, i64, f64, f64, vp, vp, i32, vp, vp, vp, i32, i32]
     lib.pinkhip_check_limits_device.argtypes = [vp, vp, i64, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_int64)]
     lib.pinkhip_integrate_device.argtypes = [vp, vp, i64, vp, vp]

@@ -462,6 +462,17 @@ class BatchSolver:
         self._check(self._lib.pinkhip_rollout_step_warm_device(self._h, ctypes.byref(desc), ctypes.c_void_p(model), ctypes.byref(args),
                                                                ctypes.byref(warm)))
 
+    def rollout_step_pairs(self, desc, model: int, args, pairs) -> bool:
+        """``pinkhip_rollout_step_pairs_device``: the whole control step in one kernel, the last ``pairs.n_rows`` dense rows
+        SelfCollisionBarrier rows of sphere pairs selected and formed on chip (:class:`pink_amd._lib.SpherePairsArgs`).
+        Returns ``False`` when the library declines the shape (no instantiation, more spheres / pairs than the stage holds)."""
+        rc = self._lib.pinkhip_rollout_step_pairs_device(self._h, ctypes.byref(desc), ctypes.c_void_p(model), ctypes.byref(args),
+                                                         ctypes.byref(pairs))
+        if rc == -5:  # PINKHIP_E_UNSUPPORTED
+            return False
+        self._check(rc)
+        return True
+
     # -- RCCL gather of dq (one handle per GPU / process) ----------------------------
     def comm_unique_id(self) -> bytes:
         """128-byte RCCL id, created on one rank and shipped to the others by the caller."""

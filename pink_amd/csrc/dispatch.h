@@ -41,6 +41,7 @@
 #define PINKHIP_WROLLOUT_TABLE(X) X(PINKHIP_DEV_NV, PINKHIP_DEV_W)
 #endif
 #endif
+#define PINKHIP_RPAIRS_TABLE(X)  // (the sphere-pair kernels are not part of a development build)
 #else
 // X(NV, MD, W): the sweep-tableau kernel with VIRTUAL dense rows ik_solve_sweepx_kernel<NV, MD, W> (ik_sweepx.h): NV
 // coordinates on the W lanes, up to MD dense rows riding in a second role of the first MD lanes (NV + MD may exceed W)
@@ -64,7 +65,11 @@
 // translation unit of minutes: a shape runs on the smallest entry that holds it.
 #define PINKHIP_WSWEEP_TABLE(X) X(16, 0, 16) X(30, 0, 32) X(34, 0, 32) X(50, 0, 64) X(64, 0, 64)
 #define PINKHIP_WROLLOUT_TABLE(X) X(16, 16) X(30, 32) X(50, 64) X(56, 64)
-#define PINKHIP_PACKED_TABLE(X)                                                                          \
+// The whole-step kernel whose LAST dense rows are SelfCollisionBarrier rows of sphere pairs, selected and formed on chip
+// (ik_rollout.h PAIRS; tu_rpairs.hip), X(NV, MD, W).  Sparse like the warm-start twins: one row per lane at W = 16, virtual
+// dense rows at W = 32, one robot per wavefront.
+#define PINKHIP_RPAIRS_TABLE(X) X(12, 4, 16) X(30, 6, 32) X(50, 14, 64)
+#define PINKHIP_PACKED_TABLE(X)                                                                      \
   X(6, 8) X(8, 8) X(12, 16) X(16, 16) X(24, 32) X(30, 32) X(32, 32) X(34, 64) X(40, 64) X(48, 64) X(50, 64) X(56, 64) X(64, 64)
 #endif
 
@@ -185,6 +190,24 @@ inline SweepChoice select_rollout_dense(int nv, int nj, int fk_doubles, int md, 
     if (8 * need * (64 / W_) + 16 <= 65536) return SweepChoice{NV_, MD_, W_};                               \
   }
   PINKHIP_ROLLOUT_DENSE_TABLE(PINKHIP_PICK)
+#undef PINKHIP_PICK
+  return SweepChoice{0, 0, 0};
+}
+
+// Sphere-pair rows (ik_rollout.h PAIRS): behind the frame positions and the constraint copies the tail keeps the world
+// centres of the spheres (3 each), the distance of every pair and five doubles per selected pair (normal, right-hand
+// side, the two sphere indices)
+constexpr int kPairsMaxSpheres = 32, kPairsMaxPairs = 64;
+constexpr int rollout_pairs_doubles(int n_spheres, int n_pairs, int n_rows) { return (3 * n_spheres + n_pairs + 5 * n_rows + 1) & ~1; }
+
+// ... {NV, MD, W} from PINKHIP_RPAIRS_TABLE: the smallest entry that holds the robot and whose LDS fits
+inline SweepChoice select_rollout_pairs(int nv, int nj, int fk_doubles, int md, int nf, int n_eqf, int pairs_doubles) {
+#define PINKHIP_PICK(NV_, MD_, W_)                                                                          \
+  if (nv <= NV_ && md <= MD_ && nj <= W_) {                                                                 \
+    const int need = rollout_lds_doubles(NV_, W_, fk_doubles, MD_, nf, n_eqf) + pairs_doubles;              \
+    if (8 * need * (64 / W_) + 16 <= 65536) return SweepChoice{NV_, MD_, W_};                               \
+  }
+  PINKHIP_RPAIRS_TABLE(PINKHIP_PICK)
 #undef PINKHIP_PICK
   return SweepChoice{0, 0, 0};
 }

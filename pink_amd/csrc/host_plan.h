@@ -140,6 +140,7 @@ enum PlanKind {
   PLAN_ROLLOUT,        // entry {NV, W} of PINKHIP_ROLLOUT_TABLE (MD = 0)
   PLAN_ROLLOUT_DENSE,  // entry {NV, MD, W} of PINKHIP_ROLLOUT_DENSE_TABLE
   PLAN_ROLLOUT_WARM,   // entry {NV, W} of PINKHIP_WROLLOUT_TABLE (MD = 0)
+  PLAN_ROLLOUT_PAIRS,  // entry {NV, MD, W} of PINKHIP_RPAIRS_TABLE
 };
 
 // One launch: `blocks` wavefronts of 64 / W instances each
@@ -218,9 +219,12 @@ inline int plan_solve(const KernelArgs &a, const char *solver_env, bool force_de
 // Validates the arguments `st` (+ `warm`: the warm-start twin of the box-only kernel) of a whole control step of the
 // model `md` (has_relative: it has relative frame slots) against the descriptor `d`, completes `ra` -- whose k holds
 // fill_desc(d) -- and picks the instantiation.
-inline int plan_rollout(const pinkhip_desc &d, const ModelDev &md, bool has_relative, const pinkhip_rollout_step &st, const pinkhip_warm *warm,
-                        const char *solver_env, RolloutArgs &ra, LaunchPlan &p, std::string &err) {
+// (pairs: the step of pinkhip_rollout_step_pairs_device, validated by plan_rollout_pairs -- the last pairs->n_rows dense
+// rows are formed from it, the barrier_* tables describe the rows in front of them)
+inline int plan_rollout_step(const pinkhip_desc &d, const ModelDev &md, bool has_relative, const pinkhip_rollout_step &st, const pinkhip_warm *warm,
+                             const pinkhip_sphere_pairs *pairs, const char *solver_env, RolloutArgs &ra, LaunchPlan &p, std::string &err) {
   p = LaunchPlan{};
+  const int n_prow = pairs ? pairs->n_rows : 0;
   LaunchPlan chosen{};
   if (warm) {
     if (const char *why = warm_refusal(ra.k, solver_env)) return refuse(err, PINKHIP_E_UNSUPPORTED, why);
@@ -236,9 +240,9 @@ inline int plan_rollout(const pinkhip_desc &d, const ModelDev &md, bool has_rela
     return refuse(err, PINKHIP_E_INVALID, "n_constraint_frames must lie in [0, 2] and come with constraint_frame / constraint_gain");
   if (d.nv != md.nv || d.n_eq != 6 * n_eqf)
     return refuse(err, PINKHIP_E_INVALID, "descriptor does not describe this model's task stack (nv, n_eq = 6 n_constraint_frames)");
-  if (st.n_limit_rows < 0 || 6 * n_eqf + st.n_limit_rows > d.md || (st.n_limit_rows > 0 && (!st.limit_rows || !st.limit_h)))
+  if (st.n_limit_rows < 0 || 6 * n_eqf + st.n_limit_rows > d.md - n_prow || (st.n_limit_rows > 0 && (!st.limit_rows || !st.limit_h)))
     return refuse(err, PINKHIP_E_INVALID, "n_limit_rows must lie in [0, md - n_eq] and come with limit_rows / limit_h");
-  if (d.md > 6 * n_eqf + st.n_limit_rows &&
+  if (d.md - n_prow > 6 * n_eqf + st.n_limit_rows &&
       (!st.barrier_frame || !st.barrier_axis || !st.barrier_sign || !st.barrier_bound || !st.barrier_gain || !st.barrier_frame2))
     return refuse(err, PINKHIP_E_INVALID, "barrier rows need the barrier_* tables, barrier_frame2 included (-1 for the rows of a position barrier)");
   if ((st.root_box || st.n_limit_rows) && md.root_nv != 6) return refuse(err, PINKHIP_E_INVALID, "a floating-base velocity limit needs a free-flyer root joint");
@@ -256,10 +260,13 @@ inline int plan_rollout(const pinkhip_desc &d, const ModelDev &md, bool has_rela
   ra.crow_b = st.const_b;
   ra.diag_e = st.diag_error;
   if (d.md > 0) {
-    const SweepChoice dc = select_rollout_dense(md.nv, md.nj, fkd, d.md, md.nf, n_eqf);
-    if (dc.NV == 0 || md.nf > 32) return refuse(err, PINKHIP_E_UNSUPPORTED, "no whole-step instantiation with barrier rows fits this model");
-    chosen = make_plan(PLAN_ROLLOUT_DENSE, dc.NV, dc.MD, dc.W, 0, d.B);
-    ra.k.lds_pitch = rollout_lds_doubles(dc.NV, dc.W, fkd, dc.MD, md.nf, n_eqf);
+    const int pd = pairs ? rollout_pairs_doubles(pairs->n_spheres, pairs->n_pairs, pairs->n_rows) : 0;
+    const SweepChoice dc = pairs ? select_rollout_pairs(md.nv, md.nj, fkd, d.md, md.nf, n_eqf, pd) : select_rollout_dense(md.nv, md.nj, fkd, d.md, md.nf, n_eqf);
+    if (dc.NV == 0 || md.nf > 32)
+      return refuse(err, PINKHIP_E_UNSUPPORTED, pairs ? "no whole-step instantiation with sphere-pair rows fits this model"
+                                                      : "no whole-step instantiation with barrier rows fits this model");
+    chosen = make_plan(pairs ? PLAN_ROLLOUT_PAIRS : PLAN_ROLLOUT_DENSE, dc.NV, dc.MD, dc.W, 0, d.B);
+    ra.k.lds_pitch = rollout_lds_doubles(dc.NV, dc.W, fkd, dc.MD, md.nf, n_eqf) + pd;
     ra.bar_frame = st.barrier_frame;
     ra.bar_axis = st.barrier_axis;
     ra.bar_sign = st.barrier_sign;
@@ -306,6 +313,46 @@ inline int plan_rollout(const pinkhip_desc &d, const ModelDev &md, bool has_rela
   ra.step = st.step;
   p = chosen;
   return PINKHIP_OK;
+}
+
+inline int plan_rollout(const pinkhip_desc &d, const ModelDev &md, bool has_relative, const pinkhip_rollout_step &st, const pinkhip_warm *warm,
+                        const char *solver_env, RolloutArgs &ra, LaunchPlan &p, std::string &err) {
+  return plan_rollout_step(d, md, has_relative, st, warm, nullptr, solver_env, ra, p, err);
+}
+
+// What pinkhip_rollout_step_pairs_device refuses about its sphere pairs `sp` before anything else is looked at (0: nothing):
+// the limits of the on-chip stage, and rows that are not the last barrier group of the descriptor's dense rows
+inline int pairs_fault(const pinkhip_desc &d, const pinkhip_sphere_pairs *sp, std::string &err) {
+  if (!sp) return refuse(err, PINKHIP_E_INVALID, "null sphere pairs");
+  if (sp->n_spheres < 1 || sp->n_pairs < 1) return refuse(err, PINKHIP_E_INVALID, "sphere pairs need at least one sphere and one pair");
+  if (sp->n_spheres > kPairsMaxSpheres) return refuse(err, PINKHIP_E_UNSUPPORTED, "more than 32 spheres");
+  if (sp->n_pairs > kPairsMaxPairs) return refuse(err, PINKHIP_E_UNSUPPORTED, "more than 64 sphere pairs");
+  if (sp->n_rows < 1 || sp->n_rows > sp->n_pairs) return refuse(err, PINKHIP_E_INVALID, "n_rows must lie in [1, n_pairs]");
+  if (!sp->sphere_joint || !sp->sphere_centre || !sp->sphere_radius || !sp->column_mask || !sp->pair_sphere)
+    return refuse(err, PINKHIP_E_INVALID, "sphere pairs: null table");
+  if (!(sp->d_min >= 0.0) || !(sp->gain == sp->gain)) return refuse(err, PINKHIP_E_INVALID, "sphere pairs: bad d_min / gain");
+  if (d.n_barriers < 1 || !d.barrier_rows || d.barrier_rows[d.n_barriers] != d.md || d.barrier_rows[d.n_barriers - 1] != d.md - sp->n_rows)
+    return refuse(err, PINKHIP_E_INVALID, "the sphere-pair rows must be the last barrier group of the dense rows (barrier_rows)");
+  return PINKHIP_OK;
+}
+
+// The whole control step with sphere-pair rows: validation, the fill of `pa` -- whose r.k holds fill_desc(d) -- and the
+// entry of PINKHIP_RPAIRS_TABLE that runs it
+inline int plan_rollout_pairs(const pinkhip_desc &d, const ModelDev &md, bool has_relative, const pinkhip_rollout_step &st,
+                              const pinkhip_sphere_pairs *sp, const char *solver_env, RolloutPairsArgs &pa, LaunchPlan &p, std::string &err) {
+  p = LaunchPlan{};
+  if (const int rc = pairs_fault(d, sp, err)) return rc;
+  pa.p.n_spheres = sp->n_spheres;
+  pa.p.n_pairs = sp->n_pairs;
+  pa.p.n_rows = sp->n_rows;
+  pa.p.sphere_joint = sp->sphere_joint;
+  pa.p.sphere_centre = sp->sphere_centre;
+  pa.p.sphere_radius = sp->sphere_radius;
+  pa.p.column_mask = sp->column_mask;
+  pa.p.pair_sphere = sp->pair_sphere;
+  pa.p.d_min = sp->d_min;
+  pa.p.gain = sp->gain;
+  return plan_rollout_step(d, md, has_relative, st, nullptr, sp, solver_env, pa.r, p, err);
 }
 
 }  // namespace pinkhip

@@ -58,11 +58,33 @@ struct RolloutArgs {
   const double *diag_e = nullptr;
 };
 
+// SelfCollisionBarrier rows of pairs of spheres attached to joints (pink/barriers/self_collision_barrier.py:85-224,
+// barrier.py:193-254): the LAST n_rows of the k.md dense rows keep dist_k - d_min >= 0 for the n_rows closest of n_pairs
+// pairs -- which pairs those are differs from robot to robot and from step to step, so they are selected on chip (pair_rows
+// of ik_rollout_instance).  For spheres the nearest points lie on the line of centres and the normal is parallel to it: the
+// reference's row n^T J_p1 + (r_1 x n)^T J_w1 - n^T J_p2 - (r_2 x n)^T J_w2 is n . (v(c_1) - v(c_2)) with v(c) the world
+// velocity of the sphere CENTRE carried by its joint -- no nearest point and no radius enters the Jacobian.
+struct PairsArgs {
+  int n_spheres = 0, n_pairs = 0, n_rows = 0;
+  const int *sphere_joint = nullptr;        // [n_spheres]
+  const double *sphere_centre = nullptr;    // [n_spheres, 3], joint frame
+  const double *sphere_radius = nullptr;    // [n_spheres]
+  const unsigned *column_mask = nullptr;    // [nv]: bit s = the joint of tangent column i is sphere s's joint or an ancestor of it
+  const int *pair_sphere = nullptr;         // [n_pairs, 2]
+  double d_min = 0.0, gain = 0.0;
+};
+
+// (the arguments of the existing kernels stay what they are: r sits at offset 0 of the kernarg segment)
+struct RolloutPairsArgs {
+  RolloutArgs r;
+  PairsArgs p;
+};
+
 // doubles of kinematics scratch per robot: joint poses, ancestor pointers, U / V blocks, frame errors (+ the errors of
 // n_crow constant rows), joint scalars
 __device__ __host__ inline int rollout_fk_doubles(int nj, int nf, int n_crow = 0) { return fk_lds_doubles(nj, nf) + 6 * nf + ((n_crow + 1) & ~1); }
 
-template <int W>
+template <int W, bool PAIRS = false>
 struct FkTerms {
   static constexpr bool kOnTheFly = true;
   static constexpr bool kKeep = true;
@@ -121,6 +143,12 @@ struct FkTerms {
   const int *eq_frame = nullptr;
   const double *eq_gain = nullptr, *eqs = nullptr;
   const int *bar_frame2 = nullptr;
+  // PAIRS: the dense rows from pair_row0 on are sphere-pair rows.  LDS (tail): world centres of the spheres pcs [3 s ..],
+  // five doubles per selected pair in pslots: the normal n (zero: the row is zero), the right-hand side, and the two
+  // sphere indices a + 32 b; pmask: bit s = this lane's column moves sphere s
+  int pair_row0 = 0;
+  unsigned pmask = 0;
+  const double *pcs = nullptr, *pslots = nullptr;
   // world velocity of frame f's origin per unit velocity of this lane's tangent column (zero unless an ancestor)
   __device__ __forceinline__ void origin_velocity(int f, double (&v)[3]) const {
     const double *pf = pfs + 3 * f;
@@ -130,6 +158,18 @@ struct FkTerms {
     v[2] = on * (lin[2] + ang[0] * pf[1] - ang[1] * pf[0]);
   }
   __device__ __forceinline__ double dense_col(int d) const {
+    if constexpr (PAIRS) {
+      if (d >= pair_row0) {  // G = -J / dt,  J_i = n . ([i moves a] (lin + ang x c_a) - [i moves b] (lin + ang x c_b))
+        const double *s = pslots + 5 * (d - pair_row0);
+        const int ab = (int)s[4], sa = ab & 31, sb = (ab >> 5) & 31;
+        const double ma = (double)((pmask >> sa) & 1u), mb = (double)((pmask >> sb) & 1u);
+        const double *ca = pcs + 3 * sa, *cb = pcs + 3 * sb;
+        const double wx = ma * ca[0] - mb * cb[0], wy = ma * ca[1] - mb * cb[1], wz = ma * ca[2] - mb * cb[2], mm = ma - mb;
+        const double vx = mm * lin[0] + ang[1] * wz - ang[2] * wy, vy = mm * lin[1] + ang[2] * wx - ang[0] * wz,
+                     vz = mm * lin[2] + ang[0] * wy - ang[1] * wx;
+        return -inv_dt * (s[0] * vx + s[1] * vy + s[2] * vz);
+      }
+    }
     if (d < n_eqr) {
       // row i of the FrameTask Jacobian of constraint c (frame_rows(), from the tail copy of U, V)
       const int c = d / 6, i = d - 6 * c, f = eq_frame[c];
@@ -158,6 +198,9 @@ struct FkTerms {
     return -bar_sign[d] * vi * inv_dt;
   }
   __device__ __forceinline__ double dense_h(int d) const {
+    if constexpr (PAIRS) {
+      if (d >= pair_row0) return pslots[5 * (d - pair_row0) + 3];
+    }
     if (d < n_eqr) {
       const int c = d / 6;
       return -eq_gain[c] * eqs[24 * c + 18 + (d - 6 * c)];  // b = -gain e (pink/solve_ik.py:147)
@@ -176,9 +219,12 @@ struct FkTerms {
 };
 
 // WARM (box-only): the tableau starts from KernelArgs::active_in and leaves its final set in active_out (ik_sweep.h)
-template <int NV, int MD, int W, bool WARM = false>
-__device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long long block) {
+// PAIRS: `a` is the member r of a RolloutPairsArgs whose member p is *pp; the last pp->n_rows dense rows are sphere-pair rows
+template <int NV, int MD, int W, bool WARM = false, bool PAIRS = false>
+__device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long long block, const PairsArgs *pp = nullptr) {
   static_assert(!WARM || MD == 0, "warm starts are box-only");
+  static_assert(!PAIRS || MD > 0, "sphere-pair rows are dense rows");
+  using Terms = FkTerms<W, PAIRS>;
   constexpr int G = kWave / W;
   const ModelDev &m = a.fk.m;
   const int lane = lane_id();
@@ -189,9 +235,15 @@ __device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long l
   // kinematics scratch at the start of this robot's share of LDS: the solve (which keeps stacking and the
   // factorisation in registers) first writes there after its last read of it; the share is the larger of the two
   double *sm = shared_base() + (long long)g * a.k.lds_pitch;
-  auto make_terms = [&](const RolloutArgs &ra) {
+  // (PAIRS: the tail of the robot's share ends with the sphere-pair area, rollout_pairs_doubles)
+  auto tail_doubles = [&](const RolloutArgs &ra, const PairsArgs *pa) {
+    int n = rollout_tail_doubles(ra.fk.m.nf, ra.n_eqf);
+    if constexpr (PAIRS) n += rollout_pairs_doubles(pa->n_spheres, pa->n_pairs, pa->n_rows);
+    return n;
+  };
+  auto make_terms = [&](const RolloutArgs &ra, const PairsArgs *pa) {
     const ModelDev &mm = ra.fk.m;
-    FkTerms<W> tt;
+    Terms tt;
     tt.es = sm + fk_lds_doubles(mm.nj, mm.nf);
     tt.UV = sm + 12 * (mm.nj + mm.nf) + ((mm.nj + 1) & ~1);  // = Jls of ik_fk_instance
     tt.nf = mm.nf, tt.n_crow = ra.n_crow, tt.col = li < mm.nv ? li : 0, tt.nvc = mm.nv, tt.crow_A = ra.crow_A;
@@ -199,7 +251,7 @@ __device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long l
     if constexpr (MD > 0) {
       tt.bar_frame = ra.bar_frame, tt.bar_axis = ra.bar_axis;
       tt.bar_sign = ra.bar_sign, tt.bar_bound = ra.bar_bound, tt.bar_gain = ra.bar_gain;
-      tt.pfs = sm + ra.k.lds_pitch - rollout_tail_doubles(mm.nf, ra.n_eqf);
+      tt.pfs = sm + ra.k.lds_pitch - tail_doubles(ra, pa);
       tt.inv_dt = 1.0 / ra.k.dt;
       tt.n_lim = ra.n_lim, tt.lim_rows = ra.lim_rows, tt.lim_h = ra.lim_h;
       tt.n_eqr = 6 * ra.n_eqf, tt.eq_frame = ra.eq_frame, tt.eq_gain = ra.eq_gain, tt.bar_frame2 = ra.bar_frame2;
@@ -208,14 +260,20 @@ __device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long l
         const int jt = mm.dof_joint[li < mm.nv ? li : 0];
         if (li < mm.nv && mm.jtype[jt] == JOINT_FREE_FLYER) tt.root_sub = li - mm.idx_v[jt];
       }
+      if constexpr (PAIRS) {
+        tt.pair_row0 = ra.k.md - pa->n_rows;
+        tt.pmask = li < mm.nv ? pa->column_mask[li] : 0u;
+        tt.pcs = sm + ra.k.lds_pitch - rollout_pairs_doubles(pa->n_spheres, pa->n_pairs, pa->n_rows);
+        tt.pslots = tt.pcs + 3 * pa->n_spheres + pa->n_pairs;
+      }
     }
     return tt;
   };
   // (frame positions out of the shared area: fMo of ik_fk_instance holds frame f's pose at sm[12 (nj + f) ..])
-  auto keep_frame_positions = [&](const RolloutArgs &ra) {
+  auto keep_frame_positions = [&](const RolloutArgs &ra, const PairsArgs *pa) {
     if constexpr (MD > 0) {
       const ModelDev &mm = ra.fk.m;
-      double *tail = sm + ra.k.lds_pitch - rollout_tail_doubles(mm.nf, ra.n_eqf);
+      double *tail = sm + ra.k.lds_pitch - tail_doubles(ra, pa);
       for (int i = li; i < 3 * mm.nf; i += W) tail[i] = sm[12 * (mm.nj + i / 3) + 9 + i % 3];
       if (ra.n_eqf > 0) {  // (kernel argument: wave-uniform)
         double *eqt = tail + ((3 * mm.nf + 1) & ~1);
@@ -228,8 +286,62 @@ __device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long l
       wave_sync();
     }
   };
+  // PAIRS: the sphere-pair stage, from the world poses of the joints (sm[12 j ..]) the kinematics left: centres (a sphere
+  // per lane), distances (a pair per lane), the n_rows closest pairs -- ascending distance, ties to the lower pair index;
+  // the rank of a pair is the number of pairs in front of it, counted over the distances in LDS (every lane reads the
+  // same address: a broadcast) -- and per selected pair its slot: normal, right-hand side, sphere indices
+  auto pair_rows = [&](const RolloutArgs &ra, const PairsArgs *pa) {
+    if constexpr (PAIRS) {
+      const int ns = pa->n_spheres, np = pa->n_pairs, nr = pa->n_rows;
+      double *pc = sm + ra.k.lds_pitch - rollout_pairs_doubles(ns, np, nr), *pd = pc + 3 * ns, *ps = pd + np;
+      for (int s = li; s < ns; s += W) {
+        const double *X = sm + 12 * pa->sphere_joint[s], *c = pa->sphere_centre + 3 * s;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) pc[3 * s + i] = X[3 * i] * c[0] + X[3 * i + 1] * c[1] + X[3 * i + 2] * c[2] + X[9 + i];
+      }
+      for (int i = li; i < 5 * nr; i += W) ps[i] = 0.0;
+      wave_sync();
+      for (int k = li; k < np; k += W) {
+        const int sa = pa->pair_sphere[2 * k], sb = pa->pair_sphere[2 * k + 1];
+        const double dx = pc[3 * sb] - pc[3 * sa], dy = pc[3 * sb + 1] - pc[3 * sa + 1], dz = pc[3 * sb + 2] - pc[3 * sa + 2];
+        pd[k] = sqrt(dx * dx + dy * dy + dz * dz) - pa->sphere_radius[sa] - pa->sphere_radius[sb];
+      }
+      wave_sync();
+      for (int k = li; k < np; k += W) {
+        const double dk = pd[k];
+        int rank = 0;
+        for (int o = 0; o < np; ++o) {
+          const double dv = pd[o];
+          rank += (dv < dk || (dv == dk && o < k)) ? 1 : 0;
+        }
+        if (rank < nr) {
+          const int sa = pa->pair_sphere[2 * k], sb = pa->pair_sphere[2 * k + 1];
+          const double ra_ = pa->sphere_radius[sa], rb_ = pa->sphere_radius[sb];
+          double u[3] = {pc[3 * sb] - pc[3 * sa], pc[3 * sb + 1] - pc[3 * sa + 1], pc[3 * sb + 2] - pc[3 * sa + 2]};
+          const double rho = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), ir = rho > 0.0 ? 1.0 / rho : 0.0;
+          // nearest points w1 = c_a + r_a u, w2 = c_b - r_b u; touching (np.allclose(w1, w2)): the row stays zero
+          double n[3], n2 = 0.0;
+          bool close = true;
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {
+            u[i] *= ir;
+            const double w1 = pc[3 * sa + i] + ra_ * u[i], w2 = pc[3 * sb + i] - rb_ * u[i];
+            n[i] = w1 - w2;
+            n2 += n[i] * n[i];
+            close = close && fabs(n[i]) <= 1e-8 + 1e-5 * fabs(w2);
+          }
+          const double in_ = (close || !(n2 > 0.0)) ? 0.0 : 1.0 / sqrt(n2);
+          double *slot = ps + 5 * rank;
+          slot[0] = n[0] * in_, slot[1] = n[1] * in_, slot[2] = n[2] * in_;
+          slot[3] = pa->gain * (dk - pa->d_min);  // (identity class-K function, barrier.py:246-254)
+          slot[4] = (double)(sa + 32 * sb);
+        }
+      }
+      wave_sync();
+    }
+  };
   // errors of the constant-row tasks, e_r = A_r (q (-) q_0) - b_r on the vector-space joints, behind the frame errors in LDS
-  auto const_row_errors = [&](const RolloutArgs &ra, const FkTerms<W> &tt) {
+  auto const_row_errors = [&](const RolloutArgs &ra, const Terms &tt) {
     if (ra.n_crow > 0) {  // wave-uniform (kernel argument)
       const ModelDev &mm = ra.fk.m;
       const int jt = mm.dof_joint[li < mm.nv ? li : 0];
@@ -246,17 +358,18 @@ __device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long l
   // have rows, examples/humanoid_jvrc.py:69-81) goes to the Goldfarb-Idnani code right away (kernel argument:
   // wave-uniform; its kinematics pass is the one below); everything else through the sweep tableau.
   const bool direct = a.k.rank_deficient != 0;
-  FkTerms<W> t = make_terms(a);
+  Terms t = make_terms(a, pp);
   int st_sweep = STATUS_ROUTED;
   if (!direct) {
-    ik_fk_instance<W, true, true, FkTerms<W>>(a.fk, block, &t, sm);
+    ik_fk_instance<W, true, true, Terms>(a.fk, block, &t, sm);
     wave_sync();
-    keep_frame_positions(a);
+    keep_frame_positions(a, pp);
+    pair_rows(a, pp);
     const_row_errors(a, t);
     // (more tableau rows than lanes: the dense rows are virtual, ik_sweepx.h -- two robots per wavefront at nv = 30
     // with barrier rows instead of one)
-    if constexpr (NV + MD > W) st_sweep = ik_sweepx_instance<NV, MD, W, FkTerms<W>>(a.k, block, &t);
-    else st_sweep = ik_sweep_instance<NV, MD, W, FkTerms<W>, WARM>(a.k, block, &t);
+    if constexpr (NV + MD > W) st_sweep = ik_sweepx_instance<NV, MD, W, Terms>(a.k, block, &t);
+    else st_sweep = ik_sweep_instance<NV, MD, W, Terms, WARM>(a.k, block, &t);
   }
   // a result that fails its KKT certificate is not integrated: the Goldfarb-Idnani code solves that robot's QP again
   // (ik_sweep.h, ik_solve_sweep_body).  It forms the rows from the kinematics like the tableau did, and the tableau's
@@ -270,13 +383,16 @@ __device__ __forceinline__ void ik_rollout_instance(const RolloutArgs &a, long l
     wave_sync();
     // (arguments read again, terms built again: nothing of them is kept in registers through the tableau loop)
     const RolloutArgs *again = kernarg_reload<RolloutArgs>(a);
-    FkTerms<W> t2 = make_terms(*again);
-    ik_fk_instance<W, true, true, FkTerms<W>>(again->fk, block, &t2, sm);
+    const PairsArgs *pp2 = nullptr;
+    if constexpr (PAIRS) pp2 = &reinterpret_cast<const RolloutPairsArgs *>(again)->p;
+    Terms t2 = make_terms(*again, pp2);
+    ik_fk_instance<W, true, true, Terms>(again->fk, block, &t2, sm);
     wave_sync();
-    keep_frame_positions(*again);
+    keep_frame_positions(*again, pp2);
+    pair_rows(*again, pp2);
     const_row_errors(*again, t2);
     // (WARM: it leaves the working set it ends on in active_out)
-    ik_packed_instance<NV, W, (MD > 0), FkTerms<W>, WARM>(again->k, block, &t2, over,
+    ik_packed_instance<NV, W, (MD > 0), Terms, WARM>(again->k, block, &t2, over,
                                                      again->k.rank_deficient ? PATH_GI : (st_sweep == STATUS_ROUTED ? PATH_ROUTED : PATH_HANDOVER));
     if (over) t.x = t2.x, t.status = t2.status;
   }
@@ -316,6 +432,13 @@ __global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_ROLLOUT(NV + MD) ik_r
 template <int NV, int W>
 __global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_ROLLOUT(NV) ik_rollout_warm_kernel(RolloutArgs a) {
   ik_rollout_instance<NV, 0, W, true>(a, block_id());
+}
+
+// ... whose last dense rows are sphere-pair rows selected and formed on chip (tu_rpairs.hip, PINKHIP_RPAIRS_TABLE): the
+// budget of the twin without them
+template <int NV, int MD, int W>
+__global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_ROLLOUT(NV + MD) ik_rollout_pairs_kernel(RolloutPairsArgs a) {
+  ik_rollout_instance<NV, MD, W, false, true>(a.r, block_id(), &a.p);
 }
 
 }  // namespace pinkhip

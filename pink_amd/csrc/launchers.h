@@ -52,7 +52,11 @@ PINKHIP_WSWEEP_TABLE(PINKHIP_DECLARE)
 PINKHIP_WROLLOUT_TABLE(PINKHIP_DECLARE)
 #undef PINKHIP_DECLARE
 
-
-
+// tu_rpairs.hip: the whole-step kernel with sphere-pair rows, one launcher per entry of PINKHIP_RPAIRS_TABLE
+struct RolloutPairsArgs;
+#define PINKHIP_LAUNCH_RPAIRS_NAME(NV, MD, W) PINKHIP_PASTE6(launch_rpairs_, NV, MD, W)
+#define PINKHIP_DECLARE(NV, MD, W) hipError_t PINKHIP_LAUNCH_RPAIRS_NAME(NV, MD, W)(hipStream_t stream, const RolloutPairsArgs &a);
+PINKHIP_RPAIRS_TABLE(PINKHIP_DECLARE)
+#undef PINKHIP_DECLARE
 
 }  // namespace pinkhip

@@ -772,6 +772,28 @@ int pinkhip_rollout_step_warm_device(pinkhip_handle *h, const pinkhip_desc *desc
   return rollout_step_launch(h, desc, m, st, warm);
 }
 
+int pinkhip_rollout_step_pairs_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_model *m,
+                                      const pinkhip_rollout_step *st, const pinkhip_sphere_pairs *pairs) {
+  if (!h || !m || !st) return fail(h, PINKHIP_E_INVALID, "null handle / model / args");
+  pinkhip::RolloutPairsArgs pa{};
+  LaunchPlan p;
+  std::string why;
+  int rc = desc ? pinkhip::pairs_fault(*desc, pairs, why) : 0;  // (before the descriptor's tables are touched)
+  if (rc) return fail(h, rc, why);
+  if ((rc = prepare(h, desc, pa.r.k))) return rc;
+  if ((rc = pinkhip::plan_rollout_pairs(*desc, m->dev, m->image.has_relative, *st, pairs, std::getenv("PINKHIP_SOLVER"), pa, p, why))) return fail(h, rc, why);
+  if (p.kind == pinkhip::PLAN_NONE) return PINKHIP_OK;
+  hipError_t e = hipErrorInvalidValue;
+  switch (p.NV * 100 + p.MD) {
+#define PINKHIP_CASE(NV, MD, W) \
+  case NV * 100 + MD: e = pinkhip::PINKHIP_LAUNCH_RPAIRS_NAME(NV, MD, W)(h->stream, pa); break;
+    PINKHIP_RPAIRS_TABLE(PINKHIP_CASE)
+#undef PINKHIP_CASE
+  }
+  PH_HIP(h, e);
+  return PINKHIP_OK;
+}
+
 int pinkhip_limits_posture_device(pinkhip_handle *h, const pinkhip_model *m, int64_t B, double dt,
                                   double config_limit_gain, const double *q, const double *q_target,
                                   int32_t target_batched, double *lb, double *ub, double *e, int32_t K,

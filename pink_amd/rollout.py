@@ -26,7 +26,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import Desc, Problem, Result, RolloutStep, Step, c_double_p, c_int32_p
+from ._lib import Desc, Problem, Result, RolloutStep, SpherePairsArgs, Step, c_double_p, c_int32_p
 from .configuration import Model
 from .exceptions import NoSolutionFound, NotWithinConfigurationLimits, PinkError
 from .utils import get_root_joint_dim
@@ -45,6 +45,37 @@ _JT = {"revolute": 0, "prismatic": 1, "free_flyer": 2}
 class NoWholeStepKernel(PinkError):
     """No instantiation of the whole-step kernel holds this model with its dense rows (``dispatch.h``:
     ``PINKHIP_ROLLOUT_DENSE_TABLE``); ``solve_ik_batch`` then evaluates the batch on the host-evaluated path."""
+
+
+MAX_SPHERES, MAX_SPHERE_PAIRS = 32, 64  # what the sphere-pair stage of the whole-step kernel holds (csrc/dispatch.h)
+
+
+def sphere_pair_tables(model: Model, pairs: Sequence[tuple]):
+    """Tables of ``pinkhip_sphere_pairs`` for the pairs of a :class:`~pink_amd.barriers.self_collision_barrier.SpherePairs`
+    query: ``(sphere_joint [ns], sphere_centre [ns, 3], sphere_radius [ns], column_mask [nv], pair_sphere [np, 2])``.
+    Identical ``(joint, centre, radius)`` spheres are stored once; bit ``s`` of ``column_mask[i]`` says that the joint of
+    tangent column ``i`` is sphere ``s``'s joint or an ancestor of it (from the model's parent table)."""
+    index, joints, centres, radii, pair_sphere = {}, [], [], [], []
+    for j1, c1, r1, j2, c2, r2 in pairs:
+        ab = []
+        for j, c, r in ((j1, c1, r1), (j2, c2, r2)):
+            c = np.asarray(c, dtype=np.float64)
+            key = (int(j), c.tobytes(), float(r))
+            if key not in index:
+                if not 0 <= int(j) < len(model.joints):
+                    raise ValueError(f"sphere on joint {j}: not a joint of the model")
+                index[key] = len(joints)
+                joints.append(int(j)), centres.append(c), radii.append(float(r))
+            ab.append(index[key])
+        pair_sphere.append(ab)
+    mask = np.zeros(model.nv, dtype=np.uint32)
+    for s_, j in enumerate(joints[:32]):
+        while j >= 0:
+            jt = model.joints[j]
+            mask[jt.idx_v:jt.idx_v + jt.nv] |= np.uint32(1 << s_)
+            j = jt.parent
+    return (np.ascontiguousarray(joints, dtype=np.int32), np.ascontiguousarray(centres, dtype=np.float64).reshape(-1, 3),
+            np.ascontiguousarray(radii, dtype=np.float64), mask, np.ascontiguousarray(pair_sphere, dtype=np.int32).reshape(-1, 2))
 
 
 class ModelDesc(ctypes.Structure):
@@ -175,7 +206,9 @@ class DeviceRollout:
         vector of a VelocityLimit built with its own numbers (the device model then carries it).  The first three need the
         whole-step kernel (``fused="kernel"``).  ``position_barriers`` takes PositionBarriers and BodySphericalBarriers
         (``pink/barriers/body_spherical_barrier.py:73-143``) in Pink's order; their frames are slots of ``frame_tasks``
-        (zero costs for a frame that carries no task).  ``constraint_slots``: equality constraints made of frame tasks,
+        (zero costs for a frame that carries no task) -- and at most ONE SelfCollisionBarrier whose ``distance_query`` is a
+        ``SpherePairs`` (``fused="kernel"`` only): its rows, selected and formed on chip per robot and step, are moved to
+        the end of the row groups (the order of the groups does not change the minimiser).  ``constraint_slots``: equality constraints made of frame tasks,
         ``(slot, gain)`` each (``pink/solve_ik.py:125-149``: ``A = J``, ``b = -gain e`` of the FrameTask of that slot of
         ``frame_tasks``, whose costs are zero when it is a constraint only); at most two.  The tables are the same for every robot and stay what they are over
         :meth:`run`: state that follows the previous step of each robot (``LowAccelerationTask.set_last_integration``,
@@ -295,8 +328,18 @@ class DeviceRollout:
                 raise ValueError(f"{what} on frame {name!r}: the frame must be a slot of frame_tasks")
             return plain[0]
 
+        # one SelfCollisionBarrier of sphere pairs: the last row group (include/pinkhip.h, pinkhip_sphere_pairs)
+        sc = [bar for bar in position_barriers if hasattr(bar, "distance_query")]
+        self._pairs_host, self.d_pairs, self._pairs = None, [], None
+        if sc:
+            self._pairs_host = self._sphere_pairs(model, sc)
+            position_barriers = [bar for bar in position_barriers if bar is not sc[0]] + sc
         bf, ba, bs, bb, bg, bf2, brow, bsafe = [], [], [], [], [], [], [n_eq + n_lim], []
         for bar in position_barriers:
+            if bar is (sc[0] if sc else None):
+                brow.append(brow[-1] + int(bar.dim))
+                bsafe.append(float(bar.safe_displacement_gain))
+                continue
             if hasattr(bar, "frames"):  # BodySphericalBarrier: one row, axis 3, bound d_min^2 (class-K function h / (1 + |h|))
                 f1, f2 = (plain_slot(n, "spherical barrier") for n in bar.frames)
                 bf.append(f1), bf2.append(f2), ba.append(3), bs.append(1.0), bb.append(float(bar.d_min) ** 2)
@@ -317,7 +360,7 @@ class DeviceRollout:
                     k += 1
             brow.append(n_eq + n_lim + len(bf))
             bsafe.append(float(bar.safe_displacement_gain))
-        self.md = n_eq + n_lim + len(bf)
+        self.md = n_eq + n_lim + len(bf) + (int(sc[0].dim) if sc else 0)
         if self.md and self.fused != "kernel":
             raise ValueError('position barriers and dense floating-base limit rows need the whole-step kernel: fused="kernel"')
         self.brow = np.ascontiguousarray(brow, dtype=np.int32)
@@ -374,6 +417,16 @@ class DeviceRollout:
                 ptr = a.alloc(max(arr.nbytes, 8))
                 a.put(ptr, arr)
                 self.d_bar.append(ptr)
+        if self._pairs_host is not None:
+            for arr in self._pairs_host:
+                ptr = a.alloc(max(arr.nbytes, 8))
+                a.put(ptr, arr)
+                self.d_pairs.append(ptr)
+            sp = SpherePairsArgs()
+            sp.sphere_joint, sp.sphere_centre, sp.sphere_radius, sp.column_mask, sp.pair_sphere = self.d_pairs
+            sp.n_spheres, sp.n_pairs, sp.n_rows = len(self._pairs_host[0]), len(self._pairs_host[4]), int(sc[0].dim)
+            sp.d_min, sp.gain = float(sc[0].d_min), float(np.asarray(sc[0].gain, dtype=float).ravel()[0])
+            self._pairs = sp
         self.d_cons = []
         if self.cons:
             for arr in (np.ascontiguousarray([s_ for s_, _ in self.cons], dtype=np.int32), np.ascontiguousarray([g_ for _, g_ in self.cons], dtype=np.float64)):
@@ -440,7 +493,30 @@ class DeviceRollout:
             raise ValueError(f"active must be a uint8 array of shape ({self.B}, {self.nv})")
         self.api.put(self.d_active, np.ascontiguousarray(active))
 
+    def _sphere_pairs(self, model, sc):
+        """Tables of the one SelfCollisionBarrier of sphere pairs the whole-step kernel forms (what it cannot hold raises)."""
+        from .barriers.self_collision_barrier import SpherePairs
+
+        bar = sc[0]
+        if len(sc) > 1:
+            raise ValueError("at most one SelfCollisionBarrier per rollout")
+        if self.fused != "kernel" or not hasattr(self.api, "rollout_step_pairs"):
+            raise ValueError('a SelfCollisionBarrier needs the whole-step kernel (fused="kernel") of a solver with rollout_step_pairs')
+        if not isinstance(bar.distance_query, SpherePairs):
+            raise ValueError("a SelfCollisionBarrier on the device needs a SpherePairs distance query")
+        gains = np.asarray(bar.gain, dtype=float).ravel()
+        if gains.size == 0 or (gains != gains[0]).any():
+            raise ValueError("a SelfCollisionBarrier on the device takes one gain for all its rows")
+        tables = sphere_pair_tables(model, bar.distance_query.pairs)
+        ns, npairs = len(tables[0]), len(tables[4])
+        if ns > MAX_SPHERES or npairs > MAX_SPHERE_PAIRS or not 1 <= int(bar.dim) <= npairs:
+            raise ValueError(f"SelfCollisionBarrier on the device: {ns} spheres (at most {MAX_SPHERES}), {npairs} pairs (at most "
+                             f"{MAX_SPHERE_PAIRS}), n_collision_pairs = {bar.dim} (1 .. pairs)")
+        return tables
+
     def _launch_whole_step(self, st, lo: int = 0) -> bool:
+        if self._pairs is not None:
+            return self.api.rollout_step_pairs(self.desc, self.dmodel, st, self._pairs)
         if self.warm_start:
             from ._lib import Warm
 
@@ -864,9 +940,10 @@ class DeviceRollout:
     def free(self) -> None:
         for name in self._BUFFERS:
             self.api.release(getattr(self, name, None))
-        for ptr in getattr(self, "d_bar", []) + getattr(self, "d_lim", []) + getattr(self, "d_extra", []) + getattr(self, "d_cons", []):
+        for ptr in (getattr(self, "d_bar", []) + getattr(self, "d_lim", []) + getattr(self, "d_extra", []) + getattr(self, "d_cons", []) +
+                    getattr(self, "d_pairs", [])):
             self.api.release(ptr)
-        self.d_bar, self.d_lim, self.d_extra, self.d_cons = [], [], [], []
+        self.d_bar, self.d_lim, self.d_extra, self.d_cons, self.d_pairs = [], [], [], [], []
         if getattr(self, "d_acc", None) is not None:
             self.api.release(self.d_acc)
             self.d_acc = None

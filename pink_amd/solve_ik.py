@@ -415,12 +415,44 @@ def _spec_of(task):
     return (name, tuple(float(v) for v in task.cost[0:3]), tuple(float(v) for v in task.cost[3:6]), float(task.gain), float(task.lm_damping))
 
 
-def _device_kinematics_plan(configurations, tasks, limits, barriers, constraints):
+def _self_collision_declined(model, bar, others: int, api) -> Optional[str]:
+    """Why the whole-step kernel does not form the rows of SelfCollisionBarrier ``bar`` (``None``: it does): one such barrier
+    per call, a :class:`~pink_amd.barriers.self_collision_barrier.SpherePairs` query, one gain for all rows,
+    ``1 <= n_collision_pairs <= len(pairs)`` (fewer pairs than rows is the host's ``InvalidCollisionPairs`` to raise), at
+    most 32 distinct spheres and 64 pairs (``include/pinkhip.h``, ``pinkhip_sphere_pairs``), a solver that has the call."""
+    from .barriers.self_collision_barrier import SpherePairs
+    from .rollout import MAX_SPHERE_PAIRS, MAX_SPHERES
+
+    if others:
+        return "more than one SelfCollisionBarrier: the whole-step kernel forms the rows of one"
+    query = bar.distance_query
+    if not isinstance(query, SpherePairs):
+        return "SelfCollisionBarrier whose distance query is not SpherePairs: only sphere pairs are evaluated on chip"
+    gains = np.asarray(bar.gain, dtype=float).ravel()
+    if gains.size == 0 or (gains != gains[0]).any():
+        return "SelfCollisionBarrier with a vector gain of unequal entries"
+    if not 1 <= int(bar.dim) <= len(query.pairs):
+        return f"SelfCollisionBarrier with n_collision_pairs = {bar.dim} outside 1 .. {len(query.pairs)} pairs"
+    if len(query.pairs) > MAX_SPHERE_PAIRS:
+        return f"SelfCollisionBarrier with {len(query.pairs)} sphere pairs (the whole-step kernel holds {MAX_SPHERE_PAIRS})"
+    nj = len(getattr(model, "joints", ()))
+    if any(not (0 <= j1 < nj and 0 <= j2 < nj) for j1, _, _, j2, _, _ in query.pairs):
+        return "SelfCollisionBarrier with a sphere on a joint the model does not have"
+    spheres = {(j, c.tobytes(), r) for j1, c1, r1, j2, c2, r2 in query.pairs for j, c, r in ((j1, c1, r1), (j2, c2, r2))}
+    if len(spheres) > MAX_SPHERES:
+        return f"SelfCollisionBarrier with {len(spheres)} distinct spheres (the whole-step kernel holds {MAX_SPHERES})"
+    if api is None or not hasattr(api() if callable(api) else api, "rollout_step_pairs"):
+        return "SelfCollisionBarrier: this solver has no rollout_step_pairs"
+    return None
+
+
+def _device_kinematics_plan(configurations, tasks, limits, barriers, constraints, api=None):
     """``(model, q [B, nq], frame task specs, target poses, posture, extras, barriers, limit gain, acceleration tables,
     velocity vector, constraints, floating-base limit)`` when the whole batch can be evaluated on the device from the configurations alone --
     FrameTasks / RelativeFrameTasks (one target per instance allowed), one PostureTask, the table-formed tasks of
     :func:`_extra_task`, the model's default limits (:func:`_default_limits_gain`), PositionBarriers (default class-K
-    function) and BodySphericalBarriers, equality constraints made of FrameTasks / RelativeFrameTasks (``pink/solve_ik.py:125-149``;
+    function), BodySphericalBarriers and one SelfCollisionBarrier of sphere pairs (:func:`_self_collision_declined`; ``api``:
+    the solver of the call, or a callable that returns it), equality constraints made of FrameTasks / RelativeFrameTasks (``pink/solve_ik.py:125-149``;
     at most two), one model
     -- else ``None``.  Frames that only a barrier or a constraint needs become slots of the device model with ZERO cost
     (``pink/tasks/task.py:148-166``: nothing enters the objective for them); ``constraints`` is a tuple of
@@ -428,12 +460,14 @@ def _device_kinematics_plan(configurations, tasks, limits, barriers, constraints
     from .barriers.barrier import Barrier
     from .barriers.body_spherical_barrier import BodySphericalBarrier
     from .barriers.position_barrier import PositionBarrier
+    from .barriers.self_collision_barrier import SelfCollisionBarrier
     from .tasks.frame_task import FrameTask
     from .tasks.relative_frame_task import RelativeFrameTask
 
     B = len(configurations)
     if B == 0:
         return None
+    n_sc = 0
     model = configurations.model if hasattr(configurations, "model") else configurations[0].model
     lim = _default_limits_gain(model, limits)
     if lim is None:
@@ -447,8 +481,13 @@ def _device_kinematics_plan(configurations, tasks, limits, barriers, constraints
         if type(bar) is PositionBarrier:
             if not bar.identity_gain_function:
                 return _declined("PositionBarrier with a class-K function of its own")
+        elif type(bar) is SelfCollisionBarrier:
+            why = _self_collision_declined(model, bar, n_sc, api)
+            if why is not None:
+                return _declined(why)
+            n_sc += 1
         elif type(bar) is not BodySphericalBarrier or np.ndim(bar.gain) > 1 or np.size(bar.gain) != 1:
-            return _declined(f"barrier {type(bar).__name__}: only PositionBarrier and BodySphericalBarrier rows are formed on chip")
+            return _declined(f"barrier {type(bar).__name__}: only PositionBarrier, BodySphericalBarrier and sphere-pair SelfCollisionBarrier rows are formed on chip")
     plan = _device_kinematics_plan_tasks(configurations, tasks)
     if plan is None:
         return _declined("a task the whole-step kernel does not form (FrameTask / RelativeFrameTask, one PostureTask, table-formed tasks shared by the batch)")
@@ -496,6 +535,8 @@ def _device_kinematics_plan(configurations, tasks, limits, barriers, constraints
         ident = np.array([1.0, 0, 0, 0, 1.0, 0, 0, 0, 1.0, 0, 0, 0])
         have = {sp[0] for sp in specs if not isinstance(sp[0], tuple)}  # (ordinary slots: a barrier needs the world pose)
         for bar in barriers:
+            if type(bar) is SelfCollisionBarrier:  # (spheres ride on joints: no frame slot)
+                continue
             for f in ((bar.frame,) if type(bar) is PositionBarrier else tuple(bar.frames)):
                 if f not in have:
                     if not any(fr.name == f for fr in getattr(model, "frames", ())):
@@ -571,6 +612,9 @@ def _explicit_floating_base_limit(model, limits):
 
 
 def _barrier_key(bar):
+    if hasattr(bar, "distance_query"):  # SelfCollisionBarrier of sphere pairs
+        pairs = tuple((j1, c1.tobytes(), r1, j2, c2.tobytes(), r2) for j1, c1, r1, j2, c2, r2 in bar.distance_query.pairs)
+        return ("self_collision", pairs, int(bar.dim), float(bar.d_min), float(np.asarray(bar.gain, float).ravel()[0]), float(bar.safe_displacement_gain))
     if hasattr(bar, "frames"):  # BodySphericalBarrier
         return ("spherical", tuple(bar.frames), float(bar.d_min), float(np.asarray(bar.gain, float).ravel()[0]), float(bar.safe_displacement_gain))
     return (bar.frame, tuple(bar.indices), None if bar.p_min is None else tuple(np.asarray(bar.p_min, float)),
@@ -931,11 +975,13 @@ def solve_ik_batch(configurations: Sequence, tasks: Sequence, dt: float, solver:
             raise PinkError(f"device_kinematics={device_kinematics!r}: True, False, None or 'frame_rows'")
         device_kinematics = None
     if not rows_only and (device_kinematics or (device_kinematics is None and len(configurations) >= 64)):
-        plan = _device_kinematics_plan(configurations, tasks, limits, barriers, constraints)
+        plan = _device_kinematics_plan(configurations, tasks, limits, barriers, constraints,
+                                       api=lambda: pool[0] if pool else (solver_handle or default_solver()))
         if plan is None and device_kinematics:
             raise PinkError("device_kinematics=True needs FrameTasks / RelativeFrameTasks (+ one PostureTask, constant-row and identity "
                             "tasks shared by the batch), the model's default limits (+ one AccelerationLimit), constraints made of at most "
-                            "two frame tasks, and barriers that are PositionBarriers or BodySphericalBarriers with the default class-K functions")
+                            "two frame tasks, and barriers that are PositionBarriers or BodySphericalBarriers with the default class-K functions "
+                            "or one SelfCollisionBarrier of sphere pairs")
     if plan is not None:
         from .batch_solver import BatchResult
         from .rollout import NoWholeStepKernel
