@@ -304,16 +304,19 @@ __device__ inline void ik_stack_small_instance(const KernelArgs &a, long long bl
     }
     if (a.c_extra) ci += a.c_extra[mine * (long long)nv + c8];
   }
-  // Levenberg-Marquardt mu per instance: dense-row partials (lanes c8 == 0, every row quarter) + diagonal-task
-  // partials (writer lanes), summed over the eight lanes of the half and the four row quarters
+  // Levenberg-Marquardt mu per instance: dense-row partials (lanes c8 == 0, every row quarter), summed over the
+  // eight lanes of the half and the four row quarters, + diagonal-task partials (writer lanes: row quarter t holds
+  // tile t's), summed over the half and fetched from that quarter.  The two are summed APART: folded into one
+  // butterfly the rounding of mu depended on which quarter held the diagonal-task part, i.e. on the instance's
+  // place in the wave (an instance out of a batch was not bit-identical to the same instance stacked alone).
+  // The sums over a half are row-level DPP (group_sum<8>), not trips through the LDS crossbar.
+  mu_d = group_sum<8>(mu_d);
 #pragma unroll
   for (int t = 0; t < TP; ++t) {
-    double m = mup[t] + (rq == t ? mu_d : 0.0);
-    m += lane_shfl(m, lane ^ 1);
-    m += lane_shfl(m, lane ^ 2);
-    m += lane_shfl(m, lane ^ 4);
+    double m = group_sum<8>(mup[t]);
     m += lane_shfl(m, lane ^ 16);
     m += lane_shfl(m, lane ^ 32);
+    m += lane_shfl(mu_d, 16 * t + col);
     // diagonal entry (i, i), i = col, of tile t sits in the lanes with rq == (col & 3), element col >> 2
     if (rq == (col & 3)) {
       const double *costb = a.cost_batched ? a.cost + inst[t] * (long long)K : a.cost;

@@ -53,12 +53,13 @@ def golden_equalities(golden, name):
     return None, None
 
 
-def random_case(nv, B, seed, Kd_tasks=2, md=0, diag=True, tight=0.05, root=0, lm=0.0, rank_deficient=False):
-    """Generic random batch: returns (packed batch, pink-form dict for the oracle)."""
+def random_case(nv, B, seed, Kd_tasks=2, md=0, diag=True, tight=0.05, root=0, lm=0.0, rank_deficient=False, Kd=None):
+    """Generic random batch: returns (packed batch, pink-form dict for the oracle).  ``Kd``: the dense tasks hold that many
+    rows in all, split evenly among them (default: one to six rows each, drawn)."""
     rng = np.random.default_rng(seed)
     tasks, Js, es, costs, gains, lms, rows = [], [], [], [], [], [], [0]
     for t in range(Kd_tasks):
-        k = int(rng.integers(1, 7))
+        k = int(rng.integers(1, 7)) if Kd is None else Kd * (t + 1) // Kd_tasks - Kd * t // Kd_tasks
         J = rng.normal(0, 0.5, size=(B, k, nv))
         if rank_deficient:
             J[:, :, nv // 2:] = 0.0

@@ -161,7 +161,10 @@ def batched_cost(solver):
 
 
 def many_dense_rows_chunked_staging(solver):
-    """Kd larger than one LDS staging chunk (rows are streamed in pieces)."""
+    """Kd = 120 at nv = 6: the stack + solve kernels stream the dense rows through their LDS staging in several chunks.
+    The stack-only call of this shape runs ik_stack_small_kernel (nv <= 8), NOT the multi-pass path of
+    ik_stack_mfma_kernel (Kd > 32 at nv > 8): that one is covered by tests/test_stack_exact.py and by
+    dense_row_count_edges below."""
     nv, B = 6, 3
     rng = np.random.default_rng(11)
     tasks, Js, es, rows = [], [], [], [0]
@@ -178,6 +181,23 @@ def many_dense_rows_chunked_staging(solver):
     pf = dict(J=np.concatenate(Js, axis=1), e=np.concatenate(es, axis=1), cost=np.ones(120), gain=np.ones(20),
               lm=np.zeros(20), rows=np.array(rows, np.int32), damping=1e-12, G=np.ascontiguousarray(G), h=h)
     check_against_oracle(solver, batch, pf)
+
+
+ROW_COUNT_EDGES = (7, 8, 9, 16, 17, 25, 33, 129)
+# (nv, md, leading coordinates without bounds, PINKHIP_SOLVER): box-only tableau, <34,0,32>, dense rows, Goldfarb-Idnani
+ROW_COUNT_SHAPES = [(16, 0, 0, None), (30, 0, 0, None), (50, 0, 0, None), (34, 0, 2, None), (30, 6, 0, None), (12, 0, 0, "packed")]
+ROW_COUNT_IDS = ["nv16", "nv30", "nv50", "nv34-free2", "nv30-md6", "nv12-packed"]
+
+
+def dense_row_count_edges(solver, nv, B, md=0, free_lead=0, kds=ROW_COUNT_EDGES):
+    """The stacking of the stack + solve kernels (8-row chunks with several in flight in stack_rows_bcast, the two
+    front columns under <34,0,32>, the Goldfarb-Idnani kernel's own staging) at the dense-row counts around their
+    chunk edges and beyond 32 and 128 rows: ``random_case`` with ``Kd`` given, held to ``check_against_oracle`` as it
+    is (which also compares H, c of the same batch through ``stack()``)."""
+    for Kd in kds:
+        batch, pf = random_case(nv, B, 7000 + 10 * nv + Kd, md=md, root=free_lead, Kd=Kd)
+        assert batch.Kd == Kd
+        check_against_oracle(solver, batch, pf)
 
 
 def empty_batch(solver):

@@ -70,6 +70,14 @@ def test_chunked_staging(emu):
     ps.many_dense_rows_chunked_staging(emu)
 
 
+@pytest.mark.parametrize("Kd", ps.ROW_COUNT_EDGES)
+@pytest.mark.parametrize("nv,md,lead,solver", ps.ROW_COUNT_SHAPES, ids=ps.ROW_COUNT_IDS)
+def test_dense_row_count_edges(emu, monkeypatch, nv, md, lead, solver, Kd):
+    if solver:
+        monkeypatch.setenv("PINKHIP_SOLVER", solver)
+    ps.dense_row_count_edges(emu, nv, B=3, md=md, free_lead=lead, kds=(Kd,))
+
+
 def test_empty_batch(emu):
     ps.empty_batch(emu)
 

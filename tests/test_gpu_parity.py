@@ -57,6 +57,14 @@ def test_edge_cases(gpu_solver):
     ps.unconstrained(gpu_solver)
 
 
+@pytest.mark.parametrize("Kd", ps.ROW_COUNT_EDGES)
+@pytest.mark.parametrize("nv,md,lead,solver", ps.ROW_COUNT_SHAPES, ids=ps.ROW_COUNT_IDS)
+def test_dense_row_count_edges(gpu_solver, monkeypatch, nv, md, lead, solver, Kd):
+    if solver:
+        monkeypatch.setenv("PINKHIP_SOLVER", solver)
+    ps.dense_row_count_edges(gpu_solver, nv, B=64, md=md, free_lead=lead, kds=(Kd,))
+
+
 @pytest.mark.parametrize("nv,n_eq,md", [(6, 2, 0), (12, 3, 2), (30, 6, 3), (50, 4, 2)])
 def test_equality_constraints(gpu_solver, nv, n_eq, md):
     ps.equality_constraints(gpu_solver, nv, n_eq, md, B=512, seed=900 + nv)
