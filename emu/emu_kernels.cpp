@@ -2,7 +2,7 @@
 // TEST INFRASTRUCTURE ONLY (see wave_emu.h).  Exposes the same struct-based
 // signature as the host entry points of include/pinkhip.h.
 #include "emu_lanes.h"
-#include "../../pink_amd/csrc/host_plan.h"
+#include "../pink_amd/csrc/host_plan.h"
 
 #include <cstdlib>
 #include <map>
@@ -62,15 +62,8 @@ pinkhip::LaneFn entry_of(const LaunchPlan &p) {
         case 4: return lane_main_stack_mfma<4>;
       }
       return nullptr;
-    case pinkhip::PLAN_SWEEP: return emu_lookup(KIND_SWEEP, p.NV, p.MD, p.W);
-    case pinkhip::PLAN_SWEEPX: return emu_lookup(KIND_SWEEPX, p.NV, p.MD, p.W);
-    case pinkhip::PLAN_PACKED: return emu_lookup(KIND_PACKED, p.NV, p.MD, p.W);  // (both DENSE variants behind one entry)
-    case pinkhip::PLAN_SWEEP_WARM: return emu_lookup(KIND_SWEEP_WARM, p.NV, p.MD, p.W);
-    case pinkhip::PLAN_ROLLOUT: return emu_lookup(KIND_ROLLOUT, p.NV, p.MD, p.W);
-    case pinkhip::PLAN_ROLLOUT_DENSE: return emu_lookup(KIND_ROLLOUT_DENSE, p.NV, p.MD, p.W);
-    case pinkhip::PLAN_ROLLOUT_WARM: return emu_lookup(KIND_ROLLOUT_WARM, p.NV, p.MD, p.W);
+    default: return emu_lookup(p.kind, p.NV, p.MD, p.W);  // (the table families; packed: both DENSE variants behind one entry)
   }
-  return nullptr;
 }
 
 int run_plan(const LaunchPlan &p, void *args) {
@@ -116,6 +109,27 @@ int rollout_step(const pinkhip_desc *d, void *mp, const pinkhip_rollout_step *st
   int rc = prepare(d, t, ra.k);
   if (!rc) rc = pinkhip::plan_rollout(*d, m->dev, m->image.has_relative, *st, warm, std::getenv("PINKHIP_SOLVER"), ra, p, g_err);
   return rc ? rc : run_plan(p, &ra);
+}
+
+// The whole control step with sphere-pair rows as pinkhip_rollout_step_pairs_device plans it (+ run: and runs it)
+int rollout_step_pairs(const pinkhip_desc *d, void *mp, const pinkhip_rollout_step *st, const pinkhip_sphere_pairs *sp, bool run, LaunchPlan &p) {
+  if (!d || !mp || !st) {
+    g_err = "null descriptor / model / args";
+    return PINKHIP_E_INVALID;
+  }
+  const EmuModel *m = static_cast<const EmuModel *>(mp);
+  int rc = run ? pinkhip::pairs_fault(*d, sp, g_err) : 0;  // (before the descriptor's tables are touched, as the library)
+  if (rc) return rc;
+  pinkhip::HostTables t;
+  pinkhip::RolloutPairsArgs pa{};
+  rc = prepare(d, t, pa.r.k);
+  if (!rc) rc = pinkhip::plan_rollout_pairs(*d, m->dev, m->image.has_relative, *st, sp, std::getenv("PINKHIP_SOLVER"), pa, p, g_err);
+  return rc || !run ? rc : run_plan(p, &pa);
+}
+
+void plan_out(const LaunchPlan &p, int out[6]) {
+  const int v[6] = {p.kind, p.NV, p.MD, p.W, p.dense, static_cast<int>(p.blocks)};
+  for (int i = 0; i < 6; ++i) out[i] = v[i];
 }
 
 }  // namespace
@@ -250,11 +264,39 @@ int pinkhip_emu_plan_solve(const pinkhip_desc *d, int out[6]) {
   LaunchPlan p;
   int rc = prepare(d, t, a);
   if (!rc) rc = pinkhip::plan_solve(a, std::getenv("PINKHIP_SOLVER"), std::getenv("PINKHIP_FORCE_DENSE") != nullptr, false, p, g_err);
-  if (rc) return rc;
-  const int v[6] = {p.kind, p.NV, p.MD, p.W, p.dense, static_cast<int>(p.blocks)};
-  for (int i = 0; i < 6; ++i) out[i] = v[i];
-  return PINKHIP_OK;
+  if (!rc) plan_out(p, out);
+  return rc;
+}
+int pinkhip_emu_rollout_step_pairs(const pinkhip_desc *d, void *mp, const pinkhip_rollout_step *st, const pinkhip_sphere_pairs *sp) {
+  LaunchPlan p;
+  return rollout_step_pairs(d, mp, st, sp, true, p);
+}
+// ... the plan of that call, in the same form; nothing runs
+int pinkhip_emu_plan_rollout_pairs(const pinkhip_desc *d, void *mp, const pinkhip_rollout_step *st, const pinkhip_sphere_pairs *sp, int out[6]) {
+  LaunchPlan p;
+  const int rc = rollout_step_pairs(d, mp, st, sp, false, p);
+  if (!rc) plan_out(p, out);
+  return rc;
+}
+// Test infrastructure: the tables of PINKHIP_FAMILIES as this library was compiled with them, one line per entry --
+// "<prefix> <kind> <dense> <NV> <MD> <W> <1: emu_lookup finds a lane entry for it and has_entry knows it>"
+const char *pinkhip_emu_table_text(void) {
+  static std::string text;
+  text.clear();
+#define PINKHIP_ROW(NV, MD, W) \
+  text += prefix + (" " + std::to_string(K)) + " " + std::to_string(D) + " " #NV " " #MD " " #W + (pinkhip::has_entry(K, NV, MD, W) && emu_lookup(K, NV, MD, W) ? " 1\n" : " 0\n");
+#define PINKHIP_FAMILY(KIND, DENSE, PREFIX, ARGS, TABLE) \
+  {                                                      \
+    const int K = pinkhip::KIND, D = DENSE;              \
+    const std::string prefix = #PREFIX;                  \
+    TABLE(PINKHIP_ROW)                                   \
+  }
+  PINKHIP_FAMILIES(PINKHIP_FAMILY)
+#undef PINKHIP_FAMILY
+#undef PINKHIP_ROW
+  return text.c_str();
 }
 const char *pinkhip_emu_last_error(void) { return g_err.c_str(); }
 const char *pinkhip_emu_warm_last_error(void) { return g_err.c_str(); }
+const char *pinkhip_emu_pairs_last_error(void) { return g_err.c_str(); }
 }

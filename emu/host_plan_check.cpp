@@ -3,7 +3,7 @@
 //   g++ -std=c++17 -fsanitize=address,undefined host_plan_check.cpp -o host_plan_check && ./host_plan_check
 // (tests/test_abi.py builds and runs it as a child process).
 #include "emu_lanes.h"
-#include "../../pink_amd/csrc/host_plan.h"
+#include "../pink_amd/csrc/host_plan.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -35,24 +35,25 @@ long long n_checked = 0;
     }                                                                                                                                     \
   } while (0)
 
-// Is {NV, MD, W} an entry of the X-macro table its kind is launched from?
+// Is {NV, MD, W} an entry of the table its kind is launched from (dispatch.h has_entry)?
 bool in_table(const LaunchPlan &p) {
-#define PINKHIP_CASE3(NV_, MD_, W_) \
-  if (p.NV == NV_ && p.MD == MD_ && p.W == W_) return true;
-#define PINKHIP_CASE2(NV_, W_) \
-  if (p.NV == NV_ && p.MD == 0 && p.W == W_) return true;
   switch (p.kind) {
     case PLAN_STACK_SMALL: return p.NV == 8 && (p.W == 8 || p.W == 32);
     case PLAN_STACK_MFMA: return p.W == 64 && p.NV % 16 == 0 && p.NV >= 16 && p.NV <= 64;
-    case PLAN_SWEEP: PINKHIP_SWEEP_TABLE(PINKHIP_CASE3) return false;
-    case PLAN_SWEEPX: PINKHIP_SWEEPX_TABLE(PINKHIP_CASE3) return false;
-    case PLAN_SWEEP_WARM: PINKHIP_WSWEEP_TABLE(PINKHIP_CASE3) return false;
-    case PLAN_ROLLOUT_DENSE: PINKHIP_ROLLOUT_DENSE_TABLE(PINKHIP_CASE3) return false;
-    case PLAN_PACKED: PINKHIP_PACKED_TABLE(PINKHIP_CASE2) return false;
-    case PLAN_ROLLOUT: PINKHIP_ROLLOUT_TABLE(PINKHIP_CASE2) return false;
-    case PLAN_ROLLOUT_WARM: PINKHIP_WROLLOUT_TABLE(PINKHIP_CASE2) return false;
   }
-  return false;
+  return has_entry(p.kind, p.NV, p.MD, p.W);
+}
+
+// One digest (FNV-1a, 64 bits) over everything walked: the inputs of every plan and rc, kind, NV, MD, W, dense, blocks
+unsigned long long digest = 1469598103934665603ULL;
+void mix(long long v) {
+  for (int i = 0; i < 8; ++i) digest = (digest ^ ((static_cast<unsigned long long>(v) >> (8 * i)) & 0xff)) * 1099511628211ULL;
+}
+void mix_plan() {
+  for (long long v : {(long long)c.nv, (long long)c.md, (long long)c.lead, (long long)c.nj, (long long)c.nf, (long long)c.n_eqf, c.B,
+                      (long long)(c.solver ? c.solver[0] + 256 * c.solver[std::string(c.solver).size() - 1] : 0), (long long)c.warm, (long long)c.rc,
+                      (long long)c.p.kind, (long long)c.p.NV, (long long)c.p.MD, (long long)c.p.W, (long long)c.p.dense, c.p.blocks})
+    mix(v);
 }
 
 // What must hold of every plan c.p that launches something for the c.B instances of c.nv coordinates (the leading `lead`
@@ -87,6 +88,7 @@ void walk_solve_plans() {
               for (bool warm : {false, true}) {
                 c.solver = solver, c.warm = warm, c.err.clear();
                 c.rc = plan_solve(a, solver, false, warm, c.p, c.err);
+                mix_plan();
                 CHECK((c.rc == PINKHIP_OK) == c.err.empty() && (c.rc == PINKHIP_OK || c.p.kind == PLAN_NONE));
                 if (warm && (md > 0 || a.rank_deficient || (solver && std::string(solver) == "packed"))) {
                   CHECK(c.rc == PINKHIP_E_UNSUPPORTED);  // what a warm start refuses
@@ -104,6 +106,7 @@ void walk_solve_plans() {
               for (bool four : {false, true}) {
                 c.err.clear();
                 c.rc = plan_stack(a, four, c.p, c.err);
+                mix_plan();
                 if (B == 0 || B > 0x7fffffffLL) {
                   CHECK(c.rc == (B ? PINKHIP_E_INVALID : PINKHIP_OK) && c.p.kind == PLAN_NONE);
                 } else {
@@ -157,7 +160,9 @@ void walk_rollout_plans() {
               fill_desc(d, t, host_table_ptrs(t), ra.k);
               const auto plan = [&](const pinkhip_rollout_step &s) {
                 c.err.clear();
-                return c.rc = plan_rollout(d, m, false, s, warm ? &w : nullptr, nullptr, ra, c.p, c.err);
+                c.rc = plan_rollout(d, m, false, s, warm ? &w : nullptr, nullptr, ra, c.p, c.err);
+                mix_plan();
+                return c.rc;
               };
               plan(st);
               CHECK((c.rc == PINKHIP_OK) == c.err.empty() && (c.rc == PINKHIP_OK || c.p.kind == PLAN_NONE));
@@ -190,6 +195,6 @@ void walk_rollout_plans() {
 int main() {
   walk_solve_plans();
   walk_rollout_plans();
-  std::printf("host_plan_check: %lld checks passed\n", n_checked);
+  std::printf("host_plan_check: %lld checks passed, plan digest %016llx\n", n_checked, digest);
   return 0;
 }

@@ -32,7 +32,7 @@
 #define PINKHIP_OCCUPANCY_FK
 #define PINKHIP_OCCUPANCY_SMALL_STACK
 
-#include "../../pink_amd/csrc/fast_sincos.h"  // rint + fma only: the emulator runs the device's sin / cos arithmetic
+#include "../pink_amd/csrc/fast_sincos.h"  // rint + fma only: the emulator runs the device's sin / cos arithmetic
 
 // element-wise kernels use blockIdx / threadIdx directly; the emulator calls their per-thread
 // bodies in a plain loop and only needs the names to exist

@@ -1,5 +1,5 @@
 // fast_sincos: the one piece of wave.h's arithmetic that needs nothing from the GPU (rint and fma only), in a
-// header of its own so that the CPU wave emulator (tests/emu/wave_emu.h) executes the very same reduction and
+// header of its own so that the CPU wave emulator (emu/wave_emu.h) executes the very same reduction and
 // polynomials as the device.  Include it behind <hip/hip_runtime.h> (device) or behind the emulator's definitions
 // of __device__ / __forceinline__ and <cmath>.
 #pragma once

@@ -1,6 +1,6 @@
 // Host-side launch plan: from a validated pinkhip_desc and the arguments of a call to the filled kernel arguments and
 // the instantiation that runs them.  Plain C++ (no HIP runtime calls, no device code), shared by the host side of the
-// library (pinkhip.hip) and by the host harness of the CPU wave emulator of the test suite (tests/emu/emu_kernels.cpp),
+// library (pinkhip.hip) and by the host harness of the CPU wave emulator of the test suite (emu/emu_kernels.cpp),
 // so that the two can never disagree about validation, argument set-up or routing.  What differs stays with each
 // side: where the broadcast tables live and how a plan becomes a launch (the library's launchers, the emulator's
 // registry of per-lane entry points).
@@ -129,29 +129,7 @@ inline FkArgs step_args(const ModelDev &m, long long B, const pinkhip_step &st) 
 
 // ---- 2. which kernel runs a filled KernelArgs ----------------------------------------------------------------------
 
-enum PlanKind {
-  PLAN_NONE = 0,  // nothing to launch (B == 0)
-  PLAN_STACK_SMALL,  // ik_stack_small_kernel<TP>: NV = 8, 64 / W instances per wavefront (W = 32: TP = 1, W = 8: TP = 4)
-  PLAN_STACK_MFMA,   // ik_stack_mfma_kernel<NV / 16> (or its staged variant), W = 64
-  PLAN_SWEEP,        // entry {NV, MD, W} of PINKHIP_SWEEP_TABLE
-  PLAN_SWEEPX,       // ... of PINKHIP_SWEEPX_TABLE
-  PLAN_PACKED,       // entry {NV, W} of PINKHIP_PACKED_TABLE, `dense`: the instantiation with the dense-row machinery (MD = 0)
-  PLAN_SWEEP_WARM,   // entry {NV, MD, W} of PINKHIP_WSWEEP_TABLE
-  PLAN_ROLLOUT,        // entry {NV, W} of PINKHIP_ROLLOUT_TABLE (MD = 0)
-  PLAN_ROLLOUT_DENSE,  // entry {NV, MD, W} of PINKHIP_ROLLOUT_DENSE_TABLE
-  PLAN_ROLLOUT_WARM,   // entry {NV, W} of PINKHIP_WROLLOUT_TABLE (MD = 0)
-  PLAN_ROLLOUT_PAIRS,  // entry {NV, MD, W} of PINKHIP_RPAIRS_TABLE
-};
-
-// One launch: `blocks` wavefronts of 64 / W instances each
-struct LaunchPlan {
-  int kind, NV, MD, W, dense;
-  long long blocks;
-};
-
-inline LaunchPlan make_plan(int kind, int NV, int MD, int W, int dense, long long B) {
-  return LaunchPlan{kind, NV, MD, W, dense, (B + 64 / W - 1) / (64 / W)};
-}
+// (PlanKind, LaunchPlan and make_plan: dispatch.h, beside the tables the kinds are launched from)
 
 // What the warm entry points refuse beyond the validation of their cold twins (NULL: nothing)
 inline const char *warm_refusal(const KernelArgs &a, const char *solver_env) {

@@ -1,5 +1,5 @@
 // Definitions shared by every kernel of the library: the kernarg struct, status codes, compile-time loop.
-// Uses only the primitives of wave.h; the CPU wave emulator under tests/emu provides the same names to run the
+// Uses only the primitives of wave.h; the CPU wave emulator under emu/ provides the same names to run the
 // kernel sources unmodified in tests.
 #pragma once
 

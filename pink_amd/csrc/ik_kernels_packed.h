@@ -15,6 +15,7 @@
 // The arithmetic per instance is the same as in ik_kernels.h (same citations apply).
 #pragma once
 
+#include "dispatch.h"
 #include "ik_common.h"
 #include "ik_stack_rows.h"
 
@@ -951,5 +952,16 @@ template <int NV, int W, bool DENSE>
 __global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_PACKED(NV, DENSE) ik_solve_packed_kernel(KernelArgs a) {
   ik_packed_instance<NV, W, DENSE>(a, block_id());
 }
+
+// The family of PINKHIP_PACKED_TABLE (dispatch.h Family): both DENSE variants, LaunchPlan::dense picks one
+template <int NV, int MD, int W, bool DENSE>
+struct Family<PLAN_PACKED, NV, MD, W, DENSE> {
+  static_assert(MD == 0, "the Goldfarb-Idnani kernel counts its dense rows at run time");
+  using Args = KernelArgs;
+  static constexpr void (*kernel)(Args) = ik_solve_packed_kernel<NV, W, DENSE>;
+  static Args prepared(const Args &a) { return a; }
+  static size_t lds_bytes(const Args &a) { return static_cast<size_t>(LdsP<NV>::bytes(DENSE ? a.md : 0, kWave / W)); }
+  static long long B(const Args &a) { return a.B; }
+};
 
 }  // namespace pinkhip

@@ -428,17 +428,56 @@ __global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_ROLLOUT(NV + MD) ik_r
   ik_rollout_instance<NV, MD, W>(a, block_id());
 }
 
-// ... whose tableau starts from the caller's active set (tu_wrollout.hip, PINKHIP_WROLLOUT_TABLE): the budget of the cold twin
+// ... whose tableau starts from the caller's active set (PINKHIP_WROLLOUT_TABLE): the budget of the cold twin
 template <int NV, int W>
 __global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_ROLLOUT(NV) ik_rollout_warm_kernel(RolloutArgs a) {
   ik_rollout_instance<NV, 0, W, true>(a, block_id());
 }
 
-// ... whose last dense rows are sphere-pair rows selected and formed on chip (tu_rpairs.hip, PINKHIP_RPAIRS_TABLE): the
+// ... whose last dense rows are sphere-pair rows selected and formed on chip (PINKHIP_RPAIRS_TABLE): the
 // budget of the twin without them
 template <int NV, int MD, int W>
 __global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_ROLLOUT(NV + MD) ik_rollout_pairs_kernel(RolloutPairsArgs a) {
   ik_rollout_instance<NV, MD, W, false, true>(a.r, block_id(), &a.p);
 }
+
+// The whole-step families (dispatch.h Family): the host plan (host_plan.h) has set lds_pitch = rollout_lds_doubles(...)
+template <int NV, int MD, int W>
+struct RolloutFamilyBase {
+  // (NV + MD > W: dense rows without lanes of their own, ik_sweepx.h)
+  static_assert(NV + MD > W ? sweepx_lds_doubles(NV, MD, W) == SweepXLds<NV, MD, W>::stride
+                            : sweep_lds_doubles(NV, MD, W) == SweepLds<NV, MD, W>::stride, "dispatch.h restates the LDS layout");
+  static_assert(packed_lds_doubles(NV, MD) == LdsP<NV>::stride(MD), "dispatch.h restates the LDS layout");
+  static const KernelArgs &core(const RolloutArgs &a) { return a.k; }
+  static const KernelArgs &core(const RolloutPairsArgs &a) { return a.r.k; }
+  template <class Args>
+  static Args prepared(const Args &a) { return a; }
+  template <class Args>
+  static size_t lds_bytes(const Args &a) { return 8 * static_cast<size_t>(core(a).lds_pitch) * (kWave / W) + 16; }
+  template <class Args>
+  static long long B(const Args &a) { return core(a).B; }
+};
+template <int NV, int W>
+struct Family<PLAN_ROLLOUT, NV, 0, W, false> : RolloutFamilyBase<NV, 0, W> {
+  using Args = RolloutArgs;
+  static constexpr void (*kernel)(Args) = ik_rollout_kernel<NV, 0, W>;
+};
+template <int NV, int MD, int W>
+struct Family<PLAN_ROLLOUT_DENSE, NV, MD, W, false> : RolloutFamilyBase<NV, MD, W> {
+  static_assert(MD > 0, "barrier rows are dense rows");
+  using Args = RolloutArgs;
+  static constexpr void (*kernel)(Args) = ik_rollout_kernel<NV, MD, W>;
+};
+template <int NV, int W>
+struct Family<PLAN_ROLLOUT_WARM, NV, 0, W, false> : RolloutFamilyBase<NV, 0, W> {
+  using Args = RolloutArgs;
+  static constexpr void (*kernel)(Args) = ik_rollout_warm_kernel<NV, W>;
+};
+template <int NV, int MD, int W>
+struct Family<PLAN_ROLLOUT_PAIRS, NV, MD, W, false> : RolloutFamilyBase<NV, MD, W> {
+  static_assert(MD > 0, "sphere-pair rows are dense rows");
+  using Args = RolloutPairsArgs;
+  static constexpr void (*kernel)(Args) = ik_rollout_pairs_kernel<NV, MD, W>;
+};
 
 }  // namespace pinkhip

@@ -1442,10 +1442,36 @@ __global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_SWEEP3(NV, MD, W) ik_
   ik_solve_sweep_body<NV, MD, W>(a, block_id());
 }
 
-// ... started from the caller's active set (tu_wsweep.hip, PINKHIP_WSWEEP_TABLE): the budgets of the cold twin
+// ... started from the caller's active set (PINKHIP_WSWEEP_TABLE): the budgets of the cold twin
 template <int NV, int MD, int W>
 __global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_SWEEP3(NV, MD, W) ik_solve_sweep_warm_kernel(KernelArgs a) {
   ik_solve_sweep_body<NV, MD, W, true>(a, block_id());
 }
+
+// The families of PINKHIP_SWEEP_TABLE and of its warm-start twin PINKHIP_WSWEEP_TABLE (dispatch.h Family)
+template <int NV, int MD, int W, bool WARM>
+struct SweepFamily {
+  static_assert(!WARM || MD == 0, "warm starts are box-only");
+  // LDS: the stated problem (H packed, c, columns of G) parked for the closing refinement step
+  static_assert(sweep_lds_doubles(NV, MD, W) == SweepLds<NV, MD, W>::stride, "dispatch.h restates the LDS layout");
+  // (front coordinates eliminated: their recovery data sits behind the area of the W-coordinate tableau)
+  static_assert(NV <= W || sweep_kernel_lds_doubles<NV, MD, W>(0) >= SweepLds<(NV <= W ? NV : W), 0, W>::stride + 2 * W + 8, "LDS of the elimination");
+  using Args = KernelArgs;
+  static Args prepared(const Args &a) {
+    Args k = a;
+    k.lds_pitch = sweep_kernel_lds_doubles<NV, MD, W>(WARM ? 0 : a.md);  // (room for the hand-over to the Goldfarb-Idnani kernel)
+    return k;
+  }
+  static size_t lds_bytes(const Args &k) { return 8 * static_cast<size_t>(k.lds_pitch) * (kWave / W) + 16; }
+  static long long B(const Args &k) { return k.B; }
+};
+template <int NV, int MD, int W>
+struct Family<PLAN_SWEEP, NV, MD, W, false> : SweepFamily<NV, MD, W, false> {
+  static constexpr void (*kernel)(KernelArgs) = ik_solve_sweep_kernel<NV, MD, W>;
+};
+template <int NV, int MD, int W>
+struct Family<PLAN_SWEEP_WARM, NV, MD, W, false> : SweepFamily<NV, MD, W, true> {
+  static constexpr void (*kernel)(KernelArgs) = ik_solve_sweep_warm_kernel<NV, MD, W>;
+};
 
 }  // namespace pinkhip

@@ -912,4 +912,19 @@ __global__ void __launch_bounds__(kWave) PINKHIP_OCCUPANCY_SWEEPX(NV, MD) ik_sol
   ik_solve_sweepx_body<NV, MD, W>(a, block_id());
 }
 
+// The family of PINKHIP_SWEEPX_TABLE (dispatch.h Family)
+template <int NV, int MD, int W>
+struct Family<PLAN_SWEEPX, NV, MD, W, false> {
+  static_assert(sweepx_lds_doubles(NV, MD, W) == SweepXLds<NV, MD, W>::stride, "dispatch.h restates the LDS layout");
+  using Args = KernelArgs;
+  static constexpr void (*kernel)(Args) = ik_solve_sweepx_kernel<NV, MD, W>;
+  static Args prepared(const Args &a) {
+    Args k = a;
+    k.lds_pitch = sweepx_kernel_lds_doubles<NV, MD, W>(a.md);  // (room for the hand-over to the Goldfarb-Idnani kernel)
+    return k;
+  }
+  static size_t lds_bytes(const Args &k) { return 8 * static_cast<size_t>(k.lds_pitch) * (kWave / W) + 16; }
+  static long long B(const Args &k) { return k.B; }
+};
+
 }  // namespace pinkhip

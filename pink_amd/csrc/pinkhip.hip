@@ -100,8 +100,18 @@ int launch_stack_mfma(pinkhip_handle *h, const KernelArgs &a) {
   return PINKHIP_OK;
 }
 
+// The launcher of plan `p` (launchers.h), called on the arguments of its family: how every table family is launched.
+// A plan without a launcher is hipErrorInvalidValue.
+template <class Args>
+int launch_plan(pinkhip_handle *h, const LaunchPlan &p, const Args &a) {
+  if (p.kind == pinkhip::PLAN_NONE) return PINKHIP_OK;
+  const pinkhip::LaunchFn<Args> fn = pinkhip::find_launcher<Args>(p);
+  PH_HIP(h, fn ? fn(h->stream, a) : hipErrorInvalidValue);
+  return PINKHIP_OK;
+}
+
 // Launch what host_plan.h planned for `a` (stack only, stack + solve, or its warm-start twin): each instantiation of the
-// stack + solve kernels is its own translation unit, reached through the launcher tables of launchers.h.
+// stack + solve kernels is its own object, reached through launch_plan().
 int launch(pinkhip_handle *h, const KernelArgs &a, bool solve, bool warm = false) {
   static const bool force_dense = std::getenv("PINKHIP_FORCE_DENSE") != nullptr;  // development: time the dense-row instantiation on a batch without dense rows
   LaunchPlan p;
@@ -111,9 +121,7 @@ int launch(pinkhip_handle *h, const KernelArgs &a, bool solve, bool warm = false
   const int rc = solve ? pinkhip::plan_solve(a, std::getenv("PINKHIP_SOLVER"), force_dense, warm, p, why) : pinkhip::plan_stack(a, a.B >= 65536, p, why);
   if (rc) return fail(h, rc, why);
   const dim3 grid(static_cast<unsigned>(p.blocks)), block(pinkhip::kWave);
-  hipError_t e = hipErrorInvalidValue;  // (a plan without a launcher)
   switch (p.kind) {
-    case pinkhip::PLAN_NONE: return PINKHIP_OK;
     case pinkhip::PLAN_STACK_SMALL:
       if (p.W == 8) {
         hipLaunchKernelGGL(pinkhip::ik_stack_small_kernel<4>, grid, block, 0, h->stream, a);
@@ -130,44 +138,8 @@ int launch(pinkhip_handle *h, const KernelArgs &a, bool solve, bool warm = false
         case 4: return launch_stack_mfma<4>(h, a);
       }
       break;
-    case pinkhip::PLAN_SWEEPX:
-      switch (p.NV * 100 + p.MD) {
-#define PINKHIP_CASE(NV, MD, W) \
-  case NV * 100 + MD: e = pinkhip::PINKHIP_LAUNCH_SWEEPX_NAME(NV, MD, W)(h->stream, a); break;
-        PINKHIP_SWEEPX_TABLE(PINKHIP_CASE)
-#undef PINKHIP_CASE
-      }
-      break;
-    case pinkhip::PLAN_SWEEP:
-      switch (p.NV * 10000 + p.MD * 100 + p.W) {
-#define PINKHIP_CASE(NV, MD, W) \
-  case NV * 10000 + MD * 100 + W: e = pinkhip::PINKHIP_LAUNCH_SWEEP_NAME(NV, MD, W)(h->stream, a); break;
-        PINKHIP_SWEEP_TABLE(PINKHIP_CASE)
-#undef PINKHIP_CASE
-      }
-      break;
-    case pinkhip::PLAN_SWEEP_WARM:
-      switch (p.NV * 100 + p.W) {
-#define PINKHIP_CASE(NV, MD, W) \
-  case NV * 100 + W: e = pinkhip::PINKHIP_LAUNCH_WSWEEP_NAME(NV, MD, W)(h->stream, a); break;
-        PINKHIP_WSWEEP_TABLE(PINKHIP_CASE)
-#undef PINKHIP_CASE
-      }
-      break;
-    case pinkhip::PLAN_PACKED:
-      switch (p.NV) {
-#define PINKHIP_CASE(NV, W)                                                                        \
-  case NV:                                                                                         \
-    e = p.dense ? pinkhip::PINKHIP_LAUNCH_PACKED_NAME(NV, W, 1)(h->stream, a)                      \
-                : pinkhip::PINKHIP_LAUNCH_PACKED_NAME(NV, W, 0)(h->stream, a);                     \
-    break;
-        PINKHIP_PACKED_TABLE(PINKHIP_CASE)
-#undef PINKHIP_CASE
-      }
-      break;
   }
-  PH_HIP(h, e);
-  return PINKHIP_OK;
+  return launch_plan(h, p, a);  // (the table families; a stack-only plan without a kernel is refused there)
 }
 
 // Validate `d`, refresh the device tables if they changed, fill the table part of `a`.
@@ -733,32 +705,7 @@ static int rollout_step_launch(pinkhip_handle *h, const pinkhip_desc *desc, cons
   LaunchPlan p;
   std::string why;
   if ((rc = pinkhip::plan_rollout(*desc, m->dev, m->image.has_relative, *st, warm, std::getenv("PINKHIP_SOLVER"), ra, p, why))) return fail(h, rc, why);
-  if (p.kind == pinkhip::PLAN_NONE) return PINKHIP_OK;
-  hipError_t e = hipErrorInvalidValue;
-  if (p.kind == pinkhip::PLAN_ROLLOUT_DENSE) {
-    switch (p.NV * 100 + p.MD) {
-#define PINKHIP_CASE(NV, MD, W) \
-  case NV * 100 + MD: e = pinkhip::PINKHIP_LAUNCH_ROLLOUT_DENSE_NAME(NV, MD, W)(h->stream, ra); break;
-      PINKHIP_ROLLOUT_DENSE_TABLE(PINKHIP_CASE)
-#undef PINKHIP_CASE
-    }
-  } else if (p.kind == pinkhip::PLAN_ROLLOUT_WARM) {
-    switch (p.NV) {
-#define PINKHIP_CASE(NV, W) \
-  case NV: e = pinkhip::PINKHIP_LAUNCH_WROLLOUT_NAME(NV, W)(h->stream, ra); break;
-      PINKHIP_WROLLOUT_TABLE(PINKHIP_CASE)
-#undef PINKHIP_CASE
-    }
-  } else {
-    switch (p.NV) {
-#define PINKHIP_CASE(NV, W) \
-  case NV: e = pinkhip::PINKHIP_LAUNCH_ROLLOUT_NAME(NV, W)(h->stream, ra); break;
-      PINKHIP_ROLLOUT_TABLE(PINKHIP_CASE)
-#undef PINKHIP_CASE
-    }
-  }
-  PH_HIP(h, e);
-  return PINKHIP_OK;
+  return launch_plan(h, p, ra);
 }
 
 int pinkhip_rollout_step_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_model *m,
@@ -782,16 +729,7 @@ int pinkhip_rollout_step_pairs_device(pinkhip_handle *h, const pinkhip_desc *des
   if (rc) return fail(h, rc, why);
   if ((rc = prepare(h, desc, pa.r.k))) return rc;
   if ((rc = pinkhip::plan_rollout_pairs(*desc, m->dev, m->image.has_relative, *st, pairs, std::getenv("PINKHIP_SOLVER"), pa, p, why))) return fail(h, rc, why);
-  if (p.kind == pinkhip::PLAN_NONE) return PINKHIP_OK;
-  hipError_t e = hipErrorInvalidValue;
-  switch (p.NV * 100 + p.MD) {
-#define PINKHIP_CASE(NV, MD, W) \
-  case NV * 100 + MD: e = pinkhip::PINKHIP_LAUNCH_RPAIRS_NAME(NV, MD, W)(h->stream, pa); break;
-    PINKHIP_RPAIRS_TABLE(PINKHIP_CASE)
-#undef PINKHIP_CASE
-  }
-  PH_HIP(h, e);
-  return PINKHIP_OK;
+  return launch_plan(h, p, pa);
 }
 
 int pinkhip_limits_posture_device(pinkhip_handle *h, const pinkhip_model *m, int64_t B, double dt,

@@ -6,7 +6,7 @@ LowAccelerationTask, JointVelocityTask -- and (FUZZ_EXTRAS=2) round 5's rows: Bo
 task, constraints=[FrameTask] -- the whole-step kernel
 (solve_ik_batch(device_kinematics=True): kinematics, rows, limits, QP on chip) against the host-evaluated path (tasks,
 limits and barriers evaluated per configuration in NumPy as Pink does, only the QP on the device).
-   python scripts/gpu_fuzz_rollout.py [first] [count]        (FUZZ_EMU=1: on the CPU wave emulator of tests/emu)"""
+   python scripts/gpu_fuzz_rollout.py [first] [count]        (FUZZ_EMU=1: on the CPU wave emulator, tests/emu/libpinkemu.so)"""
 import os
 import sys
 import time

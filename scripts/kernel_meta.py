@@ -2,7 +2,7 @@
 """Per-kernel resource usage of the gfx950 code objects in an object file / the library:
 VGPRs, SGPRs, spills, scratch, static LDS (the AMDGPU metadata notes).
 
-    python scripts/kernel_meta.py [pink_amd/csrc/libpinkhip.so | pink_amd/csrc/build/packed_30_32_0.o ...]
+    python scripts/kernel_meta.py [pink_amd/csrc/libpinkhip.so | pink_amd/csrc/build/packed_30_0_32.o ...]
 """
 import glob
 import os

@@ -3,7 +3,7 @@
 SALU, no-ops, LDS, scratch, VGPR-index reads): what DESIGN.md's per-trip table is counted from.
 
     cd pink_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -pragma-unroll-threshold=200000 \
-        -DPINKHIP_TU_NV=30 -DPINKHIP_TU_MD=0 -DPINKHIP_TU_W=32 --cuda-device-only -S tu_sweep.hip -o /tmp/k.s
+        -DPINKHIP_TU_FAMILY=sweep -DPINKHIP_TU_NV=30 -DPINKHIP_TU_MD=0 -DPINKHIP_TU_W=32 --cuda-device-only -S tu_kernel.hip -o /tmp/k.s
     python scripts/loop_stats.py /tmp/k.s
 """
 import re,sys

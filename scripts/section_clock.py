@@ -27,11 +27,13 @@ def build():
     """One-kernel profiling library: make DEV=1 SECTION_CLOCK=1 (one instantiation: CLOCK_NV / CLOCK_MD / CLOCK_W,
     default the headline one; the sweep-tableau kernel exports the counters unless PINKHIP_SOLVER=packed)."""
     nv, md, w = (os.environ.get(k, d) for k, d in (("CLOCK_NV", "30"), ("CLOCK_MD", "0"), ("CLOCK_W", "32")))
-    extra = "" if os.environ.get("PINKHIP_SOLVER") == "packed" else "-DPINKHIP_CLOCK_SWEEP"
-    if os.environ.get("PINKHIP_SOLVER") != "packed" and int(nv) + int(md) > int(w):
-        extra = "-DPINKHIP_CLOCK_SWEEPX"  # (more tableau rows than lanes: the kernel with virtual dense rows, ik_sweepx.h)
-    if os.environ.get("PINKHIP_SOLVER") == "packed" and md != "0":
-        extra = "-DPINKHIP_CLOCK_DENSE=1"
+    # -DPINKHIP_CLOCK_<prefix>: the family (dispatch.h PINKHIP_FAMILIES) whose unit exports the accessor of its counters
+    family = "packed" if os.environ.get("PINKHIP_SOLVER") == "packed" else "sweep"
+    if family == "sweep" and int(nv) + int(md) > int(w):
+        family = "sweepx"  # (more tableau rows than lanes: the kernel with virtual dense rows, ik_sweepx.h)
+    if family == "packed" and md != "0":
+        family = "pdense"
+    extra = f"-DPINKHIP_CLOCK_{family}"
     out = os.environ.get("CLOCK_OUT", "libpinkhip_clock.so")
     subprocess.run(["make", "-j4", "DEV=1", "SECTION_CLOCK=1", f"DEVNV={nv}", f"DEVMD={md}", f"DEVW={w}", f"EXTRA={extra}",
                     f"OBJDIR=build_clock_{nv}_{md}", f"OUT={out}"], cwd=ge.CSRC, check=True)

@@ -22,8 +22,8 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "k.s")
         subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-pragma-unroll-threshold=200000",
-                        "-DPINKHIP_SECTION_CLOCK", f"-DPINKHIP_TU_NV={nv}", f"-DPINKHIP_TU_W={w}", f"-DPINKHIP_TU_DENSE={dense}",
-                        "--cuda-device-only", "-S", os.path.join(CSRC, "tu_packed.hip"), "-o", out] + sys.argv[4:],
+                        "-DPINKHIP_SECTION_CLOCK", f"-DPINKHIP_TU_FAMILY={'pdense' if dense != '0' else 'packed'}", f"-DPINKHIP_TU_NV={nv}", "-DPINKHIP_TU_MD=0", f"-DPINKHIP_TU_W={w}",
+                        "--cuda-device-only", "-S", os.path.join(CSRC, "tu_kernel.hip"), "-o", out] + sys.argv[4:],
                        check=True, capture_output=True)
         lines = [l.strip() for l in open(out)]
     segs, cur, n_mark = [], {}, 0

@@ -72,60 +72,89 @@ def test_descriptor_validation(emu):
 
 
 def test_host_plan_invariants(tmp_path):
-    """tests/emu/host_plan_check.cpp, built with the address and undefined-behaviour sanitizers and run as a child process:
+    """emu/host_plan_check.cpp, built with the address and undefined-behaviour sanitizers and run as a child process:
     whatever host_plan.h plans for nv = 1..64 x md x n_free_lead x B x PINKHIP_SOLVER, cold and warm, and for the whole-step
     kernel, holds the problem, covers B, is an entry of its X-macro table and fits the LDS; the warm refusals are refused."""
     import subprocess
 
     exe = str(tmp_path / "host_plan_check")
     subprocess.run(["g++", "-std=c++17", "-Wno-psabi", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    os.path.join(ROOT, "tests", "emu", "host_plan_check.cpp"), "-o", exe], check=True)
+                    os.path.join(ROOT, "emu", "host_plan_check.cpp"), "-o", exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "checks passed" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
 
 
-def test_makefile_builds_every_instantiation_of_the_dispatch_table():
-    """dispatch.h (PINKHIP_PACKED_TABLE) is the single source of the (NV, W) instantiations; the Makefile has to
-    compile one translation unit per entry (x DENSE in {0, 1}) or the link fails only on the GPU box."""
-    import re
+def _print_objects(*args):
+    import subprocess
 
-    csrc = os.path.join(ROOT, "pink_amd", "csrc")
-    table = re.search(r"#define PINKHIP_PACKED_TABLE\(X\)\s*\\\n(.*?)#endif", open(os.path.join(csrc, "dispatch.h")).read(), re.S).group(1)
-    pairs = re.findall(r"X\((\d+), (\d+)\)", table)
-    packed = re.search(r"^PACKED\s*:=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).split()
-    assert packed == [f"{nv}_{w}" for nv, w in pairs] and len(pairs) >= 11
-    for nv, w in pairs:
-        assert int(w) >= int(nv) and int(nv) % 2 == 0 and 64 % int(w) == 0
-    # the whole-control-step kernel: a subset of the table (groups of whole 16-lane rows), one unit each
-    rt = re.search(r"#define PINKHIP_ROLLOUT_TABLE\(X\) (X\(12.*)$", open(os.path.join(csrc, "dispatch.h")).read(), re.M).group(1)
-    rpairs = re.findall(r"X\((\d+), (\d+)\)", rt)
-    rollout = re.search(r"^ROLLOUT\s*:=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).split()
-    assert rollout == [f"{nv}_{w}" for nv, w in rpairs] and set(rpairs) <= set(pairs) and all(int(w) >= 16 for _, w in rpairs)
-    # the sweep-tableau kernel: one unit per (NV, MD, W) of PINKHIP_SWEEP_TABLE, NV + MD tableau rows on W lanes
-    src = open(os.path.join(csrc, "dispatch.h")).read()
+    out = subprocess.run(["make", "-s", "print-objects", *args], cwd=os.path.join(ROOT, "pink_amd", "csrc"), capture_output=True, text=True, check=True)
+    return out.stdout.split()
+
+
+def test_makefile_builds_every_instantiation_of_the_dispatch_table():
+    """dispatch.h (PINKHIP_FAMILIES and its tables) is the single source of the instantiations; the Makefile has to compile
+    one object per entry of every family or the link fails only on the GPU box.  It derives them with the preprocessor
+    (`make print-objects`): held here to the tables as written, and to the development rule for three DEV builds."""
+    src = open(os.path.join(ROOT, "pink_amd", "csrc", "dispatch.h")).read()
+
     def table(name):
-        t = src[src.rindex(f"#define {name}(X) "):]  # (the real tables follow the development ones)
+        t = src[src.rindex(f"#define {name}(X)"):]  # (the real tables follow the development ones)
         t = t[:re.search(r"\n(?!\s*X\()", t).start()]  # the define and its continuation lines
         return re.findall(r"X\((\d+), (\d+), (\d+)\)", t)
 
-    mk = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
-    triples = table("PINKHIP_SWEEP_TABLE")
-    sweep = re.search(r"^SWEEP\s*:=\s*(.*)$", mk, re.M).group(1).split()
-    assert sweep == [f"{nv}_{md}_{w}" for nv, md, w in triples] and len(triples) >= 20
-    dense = table("PINKHIP_ROLLOUT_DENSE_TABLE")
-    rdense = re.search(r"^RDENSE\s*:=\s*(.*)$", mk, re.M).group(1).split()
-    assert rdense == [f"{nv}_{md}_{w}" for nv, md, w in dense] and len(dense) >= 4
+    families = re.findall(r"^\s*F\((PLAN_\w+), ([01]), (\w+), (\w+), (PINKHIP_\w+_TABLE)\)", src, re.M)
+    by_prefix = {prefix: table(tab) for _, _, prefix, _, tab in families}
+    assert sorted(by_prefix) == sorted(["rdense", "rpairs", "rollout", "wrollout", "sweepx", "sweep", "wsweep", "packed", "pdense"]) and len(families) == 9
+    objs = _print_objects()
+    want = [f"{prefix}_{nv}_{md}_{w}.o" for prefix, t in by_prefix.items() for nv, md, w in t]
+    assert len(objs) == len(set(objs)) and sorted(objs) == sorted(want + ["pinkhip.o"])
+    # the whole-step kernels are started first, each family from its largest entry
+    assert objs[0] == "rdense_56_8_64.o" and objs[-1] == "pinkhip.o" and objs.index("rollout_56_0_64.o") < objs.index("sweep_64_0_64.o") < objs.index("sweep_8_0_16.o")
+
+    pairs = [(nv, w) for nv, md, w in by_prefix["packed"]]
+    assert by_prefix["pdense"] == by_prefix["packed"] and all(md == "0" for _, md, _ in by_prefix["packed"]) and len(pairs) >= 11
+    for nv, w in pairs:
+        assert int(w) >= int(nv) and int(nv) % 2 == 0 and 64 % int(w) == 0
+    # the whole-control-step kernel: a subset of the table (groups of whole 16-lane rows), one unit each
+    rpairs = [(nv, w) for nv, md, w in by_prefix["rollout"]]
+    assert all(md == "0" for _, md, _ in by_prefix["rollout"]) and len(rpairs) >= 10
+    assert set(rpairs) <= set(pairs) and all(int(w) >= 16 for _, w in rpairs)
+    # the sweep-tableau kernel: one unit per (NV, MD, W) of PINKHIP_SWEEP_TABLE, NV + MD tableau rows on W lanes
+    triples, dense, virtual = by_prefix["sweep"], by_prefix["rdense"], by_prefix["sweepx"]
+    assert len(triples) >= 20 and len(dense) >= 4 and len(virtual) >= 3
     # ... and with virtual dense rows (ik_sweepx.h): NV coordinates on W lanes, MD rows in a second role of the first MD lanes
-    virtual = table("PINKHIP_SWEEPX_TABLE")
-    sweepx = re.search(r"^SWEEPX\s*:=\s*(.*)$", mk, re.M).group(1).split()
-    assert sweepx == [f"{nv}_{md}_{w}" for nv, md, w in virtual] and len(virtual) >= 3
     for nv, md, w in virtual:
         assert int(nv) <= int(w) and 1 <= int(md) <= 16 and int(nv) % 2 == 0 and int(w) in (16, 32, 64)
-    for nv, md, w in triples + dense:
+    # (the sphere-pair kernels are whole-step kernels with dense rows: held to the same rule)
+    for nv, md, w in triples + dense + by_prefix["rpairs"]:
         # one lane per tableau row, or (whole-step kernel only) virtual dense rows in an instantiated shape
         # ... or (round 6, box-only stack + solve kernel) at most two leading coordinates eliminated before the solve: NV - W
         eliminated = int(md) == 0 and 0 < int(nv) - int(w) <= 2 and (nv, md, w) in triples
         assert (int(nv) + int(md) <= int(w) or (nv, md, w) in virtual or eliminated) and int(nv) % 2 == 0 and int(w) in (16, 32, 64)
+    assert all(int(md) > 0 for _, md, _ in dense + by_prefix["rpairs"]) and set(by_prefix["rpairs"]) <= set(dense) and len(by_prefix["rpairs"]) >= 3
+    # the warm-start twins: box-only, each the twin of an entry of the cold table
+    assert set(by_prefix["wsweep"]) <= set(triples) and set(by_prefix["wrollout"]) <= set(by_prefix["rollout"])
+    assert all(md == "0" for _, md, _ in by_prefix["wsweep"] + by_prefix["wrollout"]) and len(by_prefix["wsweep"]) >= 5 and len(by_prefix["wrollout"]) >= 4
+
+    # development builds: one instantiation per family that can hold it (the PINKHIP_DEV_NV block of dispatch.h)
+    assert sorted(_print_objects("DEV=1")) == sorted(
+        ["packed_30_0_32.o", "pdense_30_0_32.o", "rollout_30_0_32.o", "sweep_30_0_32.o", "wsweep_30_0_32.o", "wrollout_30_0_32.o", "pinkhip.o"])
+    assert sorted(_print_objects("DEV=1", "DEVNV=50", "DEVMD=6", "DEVW=64")) == sorted(
+        ["packed_50_0_64.o", "pdense_50_0_64.o", "rollout_50_0_64.o", "sweep_50_6_64.o", "sweepx_50_6_64.o", "rdense_50_6_64.o", "pinkhip.o"])
+    # (more coordinates than lanes: front coordinates eliminated in the tableau kernels, the others hold all of them on 64 lanes)
+    assert sorted(_print_objects("DEV=1", "DEVNV=34", "DEVW=32")) == sorted(
+        ["packed_34_0_64.o", "pdense_34_0_64.o", "rollout_34_0_64.o", "sweep_34_0_32.o", "wsweep_34_0_32.o", "wrollout_34_0_64.o", "pinkhip.o"])
+
+
+def test_emulator_has_a_lane_entry_for_every_table_entry(emu):
+    """Every entry of every family of PINKHIP_FAMILIES has a registered lane entry in the emulator (a missing one used to
+    surface only when some parity case happened to plan it), and the emulator was compiled with the tables `make` builds."""
+    emu.lib.pinkhip_emu_table_text.restype = ctypes.c_char_p
+    rows = [ln.split() for ln in emu.lib.pinkhip_emu_table_text().decode().splitlines()]
+    assert len(rows) >= 81 and all(len(r) == 7 for r in rows)
+    assert [r for r in rows if r[6] != "1"] == []
+    assert sorted(f"{r[0]}_{r[3]}_{r[4]}_{r[5]}.o" for r in rows) == sorted(o for o in _print_objects() if o != "pinkhip.o")
+    assert {r[0]: r[2] for r in rows}["pdense"] == "1" and sum(r[2] == "1" for r in rows) == sum(r[0] == "packed" for r in rows)
 
 
 def test_headline_kernel_has_no_register_spills(built):

@@ -46,7 +46,7 @@ class _Emu:
         self.s = solver
 
     def four_tiles(self, B):
-        return B % 2 == 1  # (tests/emu/emu_kernels.cpp: the emulator picks the four-tile packing by B % 2)
+        return B % 2 == 1  # (emu/emu_kernels.cpp: the emulator picks the four-tile packing by B % 2)
 
     def stack(self, batch):
         return self.s.stack(batch)
