@@ -261,6 +261,13 @@ inline int group_bcast_i(int v, int src) {
   if (src < 0 || src >= W) std::abort();
   return lane_shfl_i(v, (emu().cur & ~(W - 1)) | src);
 }
+// (wave.h: the two rows of 16 lanes of every 32-lane half exchange their values; a = the even row's, b = the odd row's)
+inline void row_pair(double v, double &a, double &b) {
+  const int l = emu().cur;
+  const double o = emu_exchange(v, l ^ 16, 36);
+  a = (l & 16) ? o : v;
+  b = (l & 16) ? v : o;
+}
 // broadcast-FMA (wave.h: v_fmac_f64 with a DPP row_newbcast operand): here one rendezvous per use
 template <int W>
 struct Bcast {
