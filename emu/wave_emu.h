@@ -220,6 +220,34 @@ inline unsigned long long wave_ballot(bool p) {
   emu_rendezvous(43);
   return r;
 }
+// lane masks (wave.h): the inverse ballot is a plain bit test of this lane's bit, the builders are the same arithmetic
+inline bool lane_pred(unsigned long long mask) { return ((mask >> emu().cur) & 1ull) != 0; }
+template <int W>
+constexpr unsigned long long mask_lane(int J) {
+  unsigned long long m = 0;
+  for (int g = 0; g < 64 / W; ++g) m |= 1ull << (g * W + J);
+  return m;
+}
+template <int W>
+constexpr unsigned long long mask_lanes_below(int J) {
+  const unsigned long long low = (J >= 64) ? ~0ull : ((1ull << J) - 1ull);
+  unsigned long long m = 0;
+  for (int g = 0; g < 64 / W; ++g) m |= low << (g * W);
+  return m;
+}
+template <int W>
+constexpr unsigned long long mask_groups(unsigned bits) {
+  constexpr unsigned long long all = (W >= 64) ? ~0ull : ((1ull << (W & 63)) - 1ull);
+  unsigned long long m = 0;
+  for (int g = 0; g < 64 / W; ++g) m |= ((bits >> g) & 1u) ? (all << (g * W)) : 0ull;
+  return m;
+}
+template <int W>
+constexpr unsigned long long mask_groups_of_lane(unsigned long long m, int K) {
+  unsigned bits = 0;
+  for (int g = 0; g < 64 / W; ++g) bits |= static_cast<unsigned>((m >> (g * W + K)) & 1ull) << g;
+  return mask_groups<W>(bits);
+}
 template <int W>
 inline int group_first_lane(bool p) {
   Emu &e = emu();
@@ -337,6 +365,7 @@ inline float key32_packf(float v, int payload) {
   std::memcpy(&r, &b, 4);
   return r;
 }
+inline float key32_packf_quiet(float v, int payload) { return key32_packf(v, payload); }  // (wave.h: the same two clamps)
 inline int key32_payload(float k) {
   int b;
   std::memcpy(&b, &k, 4);

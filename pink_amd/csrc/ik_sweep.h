@@ -137,6 +137,16 @@ static __device__ unsigned long long pinkhip_clock[16];  // one copy per transla
 #ifndef PINKHIP_SWEEP_LATE_ADDRESSES
 #define PINKHIP_SWEEP_LATE_ADDRESSES(Src) (!Src::kOnTheFly)
 #endif
+// The box-only loop's control state (running, refined, at_point: uniform over a group, and so is every condition that changes
+// them) as 64-bit lane masks in scalar registers (wave.h: lane_pred), with the iteration cap, Murty's switch and the verdict
+// on a pivot of the wrong sign behind scalar branches.  None of it touches the arithmetic.  (off -- the whole-step kernel,
+// which is short of scalar registers too: its device code is what it was.  The loops with dense rows keep their bools:
+// need_sel, ppm_mode and restoring change under conditions that are no single compare.  Two more uses of the masks were
+// timed alone and taken out again -- the initial sweeps' `want` from the scalar ballot and the closing product's `j > li`:
+// each traded VALU for about twice as many SALU instructions and gained 0.2 %)
+#ifndef PINKHIP_SWEEP_LANE_MASKS
+#define PINKHIP_SWEEP_LANE_MASKS(Src) (!Src::kOnTheFly)
+#endif
 
 namespace pinkhip {
 
@@ -180,9 +190,11 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   static_assert((W == 16 || W == 32 || W == 64) && NT <= W && NV % 2 == 0 && MD >= 0, "group of whole rows of 16 lanes");
   constexpr bool DENSE = MD > 0;
   constexpr bool DREG = PINKHIP_SWEEP_DIAG_REGISTER(Src);
+  constexpr bool LM = PINKHIP_SWEEP_LANE_MASKS(Src);
   constexpr bool PPM = !DENSE && PINKHIP_SWEEP_PPM;                                  // box-only: the whole iteration
   constexpr bool PPMD = DENSE && PINKHIP_SWEEP_PPM && PINKHIP_SWEEP_PPM_DENSE && (!Src::kOnTheFly || PINKHIP_ROLLOUT_PPM_DENSE);  // dense rows: in front of the dual method
   constexpr bool PPX = PPM || PPMD;
+  constexpr bool LMP = LM && PPM;  // the tableau loop's control state as masks: the box-only loop
   static_assert(!WARM || PPM, "a warm start is a start of the principal pivoting of the box-only instantiations");
   constexpr int G = kWave / W;
   constexpr double INF = INFINITY;
@@ -658,6 +670,17 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   bool running = (status == STATUS_OPTIMAL);
   bool need_sel = true;
   bool refined = (status == STATUS_ROUTED);  // the closing refinement step(s) of this group have been taken
+  // (LMP) The control state the box-only loop changes -- running, refined, at_point: uniform over a group, and so is every
+  // condition that changes them -- crosses the loop edge as 64-bit lane masks in scalar registers.  A bool that is carried
+  // round a loop is a per-lane value: a v_cndmask 0, 1 at the edge and a v_cmp_ne in front of every branch on it.  The
+  // masks change in wave-uniform control flow only, by scalar arithmetic with the ballot OF A COMPARE (which is the
+  // compare's own result; the ballot of any other bool is that same v_cndmask / v_cmp_ne pair); the bools of a trip are
+  // read off them with lane_pred at its top, "some group" is mask != 0.
+  unsigned long long run_m = 0, ref_m = 0, atp_m = 0;
+  if constexpr (LMP) {
+    run_m = wave_ballot(status == STATUS_OPTIMAL);
+    ref_m = wave_ballot(status == STATUS_ROUTED);
+  }
   int nref = 0;
   double dprev = 0.0;  // largest entry of the previous refinement step
 
@@ -852,8 +875,18 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   bool restoring = false;
   const bool cand_lane = in || (DENSE && dlane && dr >= n_eq);
   const bool eq_lane = DENSE && dlane && dr < n_eq;
+  // (LMP) trips of this wave so far, a scalar: no group's `it` is above it, so the tests that fire once in many trips --
+  // the iteration cap, Murty's switch -- sit behind one scalar compare against the smaller of their thresholds.  `it`
+  // itself stays per lane.
+  int trips = 0;
+  int rare_after = (PINKHIP_SWEEP_PPM_MURTY_AFTER(nv + md) < max_iter) ? PINKHIP_SWEEP_PPM_MURTY_AFTER(nv + md) : max_iter;
+  if constexpr (LMP) rare_after = wave_uniform(rare_after);  // (kernel arguments: the same in every lane, and now a scalar)
 
   for (;;) {
+    if constexpr (LMP) {
+      ++trips;
+      running = lane_pred(run_m), refined = lane_pred(ref_m), at_point = lane_pred(atp_m);
+    }
     // (a) entering constraint, for the groups that have none pending: the violated constraint that is farthest away
     // in the metric of the objective, violation / sqrt(n^T Z n) with Z the reduced inverse Hessian -- n^T Z n is the
     // diagonal entry -T[i][i] (free coordinate i: Z_ii; inactive row: g Z g^T).
@@ -875,7 +908,10 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
     int nb_src = 0;     // the index that is exchanged is nonbasic (enters the basis)
     bool iseq = false;  // ... is the next equality
     if constexpr (PPX) {
-      if (wave_any(running && ppm_mode)) {
+      bool some_sel;
+      if constexpr (LMP) some_sel = run_m != 0;
+      else some_sel = wave_any(running && ppm_mode);
+      if (some_sel) {
         const bool sel = running && ppm_mode;
         // one test for every coordinate: a free one against its box (with the usual thresholds), a fixed one through
         // -g against (-inf, 0] at its lower bound resp. [0, inf) at its upper bound (exact sign); a dense row through
@@ -896,8 +932,24 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
         const float wz = (zf > 1e-30f) ? approx_rcpf(zf) : 1e30f;
         const float fv = static_cast<float>(viol);
         float key = -(fv * fv) * wz;
-        if (it > PINKHIP_SWEEP_PPM_MURTY_AFTER(nv + md)) key = static_cast<float>(li - 64);  // least index
-        const float best32 = group_min32<W>((vlo || vup) ? key32_packf(key, li | (vlo ? 0 : 64) | (nonbasic ? 128 : 0)) : 3.0e38f);
+        if constexpr (LMP) {
+          if (trips > rare_after) {  // (a scalar branch, kept one: the empty asm keeps its body from becoming a select on every trip)
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(key));
+#endif
+            if (it > PINKHIP_SWEEP_PPM_MURTY_AFTER(nv + md)) key = static_cast<float>(li - 64);  // least index
+          }
+        } else {
+          if (it > PINKHIP_SWEEP_PPM_MURTY_AFTER(nv + md)) key = static_cast<float>(li - 64);  // least index
+        }
+        // The key is a candidate's only where (vlo || vup), and there it is no NaN: the violation it is made of passed a
+        // `<`, its square is in [0, inf], the weight in (0, 1e30] -- and zero only for an infinite diagonal entry, where
+        // inf * 0 is the one NaN left: a quiet one, which the raw v_min_f32 of key32_packf_quiet drops as fminf does.  The
+        // two clamps stay: the product underflows to -0.0f for a multiplier that is wrong by less than 1e-23 and
+        // overflows to -inf at a weight of 1e30 from a violation of 20 on.
+        float best32;
+        if constexpr (LMP) best32 = group_min32<W>((vlo || vup) ? key32_packf_quiet(key, li | (vlo ? 0 : 64) | (nonbasic ? 128 : 0)) : 3.0e38f);
+        else best32 = group_min32<W>((vlo || vup) ? key32_packf(key, li | (vlo ? 0 : 64) | (nonbasic ? 128 : 0)) : 3.0e38f);
         bool conv = false;
         if (sel) {
           if (DENSE && !restoring && eq_next < n_eq) {
@@ -920,6 +972,8 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
             nb_src = pl >> 7;
           }
         }
+        // (LMP: a group without a candidate is done -- the compare's own ballot, taken out of the mask by scalar arithmetic)
+        if constexpr (LMP) run_m &= ~wave_ballot(!(best32 < 0.0f));
         if constexpr (DENSE) {
           if (conv) {
             // ... into the variables of the dual method and of the closing trips: the point, the multipliers (slacks of
@@ -985,7 +1039,18 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
         }
       }
     }
-    if (running) {
+    if constexpr (LMP) {
+      if (running) ++it;
+      if (trips > rare_after) {  // (wave-uniform, a scalar compare: an ordinary trip pays the increment alone)
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(it));
+#endif
+        const bool over = it > max_iter;
+        if (running && over) status = STATUS_MAX_ITER;
+        running = running && !over;
+        run_m &= ~wave_ballot(over);
+      }
+    } else if (running) {
       if (++it > max_iter) {
         status = STATUS_MAX_ITER;
         running = false;
@@ -996,9 +1061,17 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
     }
     // once no group of the wave is running any more, closing trips take the refinement steps of all of them
     // (`closing` is wave-uniform: an ordinary trip pays one ballot and scalar branches for all of this)
-    const bool closing = !wave_any(running);
+    bool closing;
+    if constexpr (LMP) closing = run_m == 0;
+    else closing = !wave_any(running);
     const bool ref = closing && !refined;
-    if (closing && !wave_any(ref)) break;
+    // (the masks are compared with "all 64 lanes": every lane of the wave is active at every ballot of this loop -- no
+    // group returns early, the surplus groups of the last wave redo the last instance -- which the loop relies on)
+    if constexpr (LMP) {
+      if (closing && ~ref_m == 0) break;
+    } else {
+      if (closing && !wave_any(ref)) break;
+    }
     const bool act = running;
     PINKHIP_TICK(3);  // selection
 
@@ -1015,6 +1088,7 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
             if (state != 0) x = (state == 1) ? lbv : ubv;
             at_point = true;
           }
+          if constexpr (LMP) atp_m = ~0ull;  // (every group of the wave is in its closing trips)
         }
         rres = residual(cert_fails);
         if constexpr (PPX) {
@@ -1090,7 +1164,13 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
         // (a closing trip that asks for another one falls through the rest of the body, everything masked off: a
         // second back edge -- `continue` -- makes the register allocator keep two copies of T and move one onto the
         // other per trip)
-        if (!wave_any(!refined)) break;
+        // (LMP: the one ballot of a bool that is no compare -- once per closing trip, in wave-uniform control flow)
+        if constexpr (LMP) {
+          ref_m = wave_ballot(refined);
+          if (~ref_m == 0) break;
+        } else {
+          if (!wave_any(!refined)) break;
+        }
       }
     } else {
       col = column_of(act ? src : -1);
@@ -1117,7 +1197,19 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
           // The pivot has the sign of the curvature it stands for; anything else: H is not positive definite on this set
           // (or the tableau is no inverse any more) -- the Goldfarb-Idnani code, whose Cholesky factorisation decides
           // that, takes the instance
-          if (actP && !(pv * sgp > 0.0)) {
+          if constexpr (LMP) {
+            // (the compare's ballot, restricted to the groups that exchange; the verdict behind a scalar branch)
+            const unsigned long long bad_m = wave_ballot(!(pv * sgp > 0.0)) & run_m;
+            if (bad_m != 0) {
+#if defined(__HIP_DEVICE_COMPILE__)
+              asm volatile("" : "+v"(status));
+#endif
+              if (lane_pred(bad_m)) status = STATUS_NOT_PD;
+            }
+            run_m &= ~bad_m;
+            running = lane_pred(run_m);
+            act2 = running;
+          } else if (actP && !(pv * sgp > 0.0)) {
             status = STATUS_NOT_PD;
             running = false;
             act2 = false;

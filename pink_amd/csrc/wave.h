@@ -315,6 +315,51 @@ __device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __bui
 // A value every lane of the wave agrees on, as a scalar the compiler keeps in an SGPR and branches on with s_cbranch_scc.
 __device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// ---- lane masks: predicates that are known per lane at compile time, or that are uniform over a group ----
+// A wave-uniform 64-bit mask as a per-lane bool (bit l = lane l): the mask goes to VCC / a scalar register pair and is
+// the condition of the select or branch itself -- no v_cmp against the lane index, no v_cndmask 0, 1 to carry a bool
+// across a loop edge.  `mask` must be wave-uniform (a literal, a ballot, scalar arithmetic on those).
+__device__ __forceinline__ bool lane_pred(unsigned long long mask) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_inverse_ballot_w64(mask);
+#else  // the host pass of hipcc only parses device functions
+  return (mask >> (threadIdx.x & 63)) & 1;
+#endif
+}
+// Builders of the usual masks for groups of W lanes (W = 16, 32, 64; 64 / W groups per wave).  No kernel uses one today (the
+// two uses that did were timed and taken out): they are the primitive's set, held to NumPy by
+// tests/test_lane_mask_primitives.py.
+// lane J of every group (li == J)
+template <int W>
+__host__ __device__ constexpr unsigned long long mask_lane(int J) {
+  unsigned long long m = 0;
+  for (int g = 0; g < 64 / W; ++g) m |= 1ull << (g * W + J);
+  return m;
+}
+// the lanes below J of every group (li < J; J = 0: none, J = W: all)
+template <int W>
+__host__ __device__ constexpr unsigned long long mask_lanes_below(int J) {
+  const unsigned long long low = (J >= 64) ? ~0ull : ((1ull << J) - 1ull);
+  unsigned long long m = 0;
+  for (int g = 0; g < 64 / W; ++g) m |= low << (g * W);
+  return m;
+}
+// all lanes of the groups whose bit is set in a per-group bit field (bit g = group g); scalar arithmetic at run time
+template <int W>
+__host__ __device__ constexpr unsigned long long mask_groups(unsigned bits) {
+  constexpr unsigned long long all = (W >= 64) ? ~0ull : ((1ull << (W & 63)) - 1ull);
+  unsigned long long m = 0;
+  for (int g = 0; g < 64 / W; ++g) m |= ((bits >> g) & 1u) ? (all << (g * W)) : 0ull;
+  return m;
+}
+// ... the groups whose lane K has its bit set in a ballot `m` (bit g W + K of m = the flag of group g)
+template <int W>
+__host__ __device__ constexpr unsigned long long mask_groups_of_lane(unsigned long long m, int K) {
+  unsigned bits = 0;
+  for (int g = 0; g < 64 / W; ++g) bits |= static_cast<unsigned>((m >> (g * W + K)) & 1ull) << g;
+  return mask_groups<W>(bits);
+}
+
 // Index inside its group of W lanes of the first lane whose predicate holds (W if none): one ballot, the group's bits
 // shifted down, count of trailing zeros -- no LDS crossbar.
 template <int W>
@@ -498,6 +543,20 @@ __device__ __forceinline__ float key32_pack(double v, int payload) {
 }
 __device__ __forceinline__ float key32_packf(float v, int payload) {
   const float f = fmaxf(fminf(v, -1.17549435e-38f), -3.0e38f);
+  return __int_as_float((__float_as_int(f) & ~0xFF) | (payload & 0xFF));
+}
+// ... for a key that is never a SIGNALLING NaN (anything arithmetic produced): the same two clamps as raw v_min_f32 /
+// v_max_f32 with the bounds as literals, without the canonicalising v_max_f32 x, x that fminf() puts in front of them in
+// IEEE mode.  A quiet NaN still loses against the bound, as in fminf: the result is key32_packf's bit for bit.
+// (one v_med3_f32 would do for numbers, but returns the lower end for a NaN where the two clamps return the upper)
+__device__ __forceinline__ float key32_packf_quiet(float v, int payload) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  float f;
+  asm("v_min_f32 %0, 0x80800000, %1" : "=v"(f) : "v"(v));  // -1.17549435e-38f
+  asm("v_max_f32 %0, 0xff61b1e6, %1" : "=v"(f) : "v"(f));  // -3.0e38f
+#else  // the host pass of hipcc only parses device functions
+  const float f = fmaxf(fminf(v, -1.17549435e-38f), -3.0e38f);
+#endif
   return __int_as_float((__float_as_int(f) & ~0xFF) | (payload & 0xFF));
 }
 __device__ __forceinline__ int key32_payload(float k) { return __float_as_int(k) & 0xFF; }
