@@ -193,6 +193,19 @@ struct TabRegs {
     }
     return (p >= 0) ? c : 0.0;
   }
+  // ... for a p that is ALWAYS a column (0 <= p < NT in every lane) and a predicate of its own for "none" (a lane mask:
+  // ik_sweep.h, PINKHIP_SWEEP_SPLIT_CLOSING): no -1 to select in front of the scalar reads, to clamp and to compare behind them
+  template <int W>
+  __device__ __forceinline__ double at_group_uniform_on(int p, bool on) const {
+    constexpr int G = kWave / W;
+    static_assert(G == 1 || G == 2, "one or two reads per wave");
+    double c = at_uniform(bcast_i(p, 0));
+    if constexpr (G == 2) {
+      const double c1 = at_uniform(bcast_i(p, W));
+      c = (lane_id() >= W) ? c1 : c;
+    }
+    return on ? c : 0.0;
+  }
 };
 
 // two doubles written / read as one 16-byte LDS access

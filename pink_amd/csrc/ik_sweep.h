@@ -147,6 +147,23 @@ static __device__ unsigned long long pinkhip_clock[16];  // one copy per transla
 #ifndef PINKHIP_SWEEP_LANE_MASKS
 #define PINKHIP_SWEEP_LANE_MASKS(Src) (!Src::kOnTheFly)
 #endif
+// The ordinary trip of the box-only loop on an issue-slot diet: vector, scalar and branch instructions counted together
+// (three in-order waves per SIMD: a wave's own scalar, branch and wait time decides how often one of its vector
+// instructions is ready).  It needs the lane masks above and touches neither the arithmetic nor the order of the exchanges.
+// (off -- the whole-step kernel, short of registers: its device code is what it was; the loops with dense rows and
+// ik_sweepx.h are not touched)
+//   SPLIT_CLOSING   a group of the box-only loop never returns from closing to exchanging: `while (some group runs)
+//                   { ordinary trip }`, then the closing trips in a loop of their own.  Off the ordinary trip: the closing /
+//                   ref tests, the `act ? src : -1` selects in front of the closing product, the masked-off fall-through
+//                   and the loop-edge copies of status, nref, dprev.
+// (Timed and taken out again: the exchanged lane's state as selects under one per-lane predicate, 139 / 63 -> 140 / 58 VALU /
+// SALU per trip and 0.47 % SLOWER on the MI355X than the split alone -- DESIGN.md 3, profiles/trip_issue_ab.json.)
+// With the switch on -- every default build of the box-only stack + solve kernels -- the `if constexpr (LMP)` arms of the
+// single loop are not compiled: they stay as the reference the split loops are held to (PINKHIP_SWEEP_SPLIT_CLOSING(Src)=0
+// builds them; scripts/loop_stats.py and the A/B of DESIGN.md 3 compare the two).
+#ifndef PINKHIP_SWEEP_SPLIT_CLOSING
+#define PINKHIP_SWEEP_SPLIT_CLOSING(Src) (!Src::kOnTheFly)
+#endif
 
 namespace pinkhip {
 
@@ -195,6 +212,7 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   constexpr bool PPMD = DENSE && PINKHIP_SWEEP_PPM && PINKHIP_SWEEP_PPM_DENSE && (!Src::kOnTheFly || PINKHIP_ROLLOUT_PPM_DENSE);  // dense rows: in front of the dual method
   constexpr bool PPX = PPM || PPMD;
   constexpr bool LMP = LM && PPM;  // the tableau loop's control state as masks: the box-only loop
+  constexpr bool SPLIT = LMP && PINKHIP_SWEEP_SPLIT_CLOSING(Src);   // ... its closing trips in a loop of their own
   static_assert(!WARM || PPM, "a warm start is a start of the principal pivoting of the box-only instantiations");
   constexpr int G = kWave / W;
   constexpr double INF = INFINITY;
@@ -882,6 +900,170 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   int rare_after = (PINKHIP_SWEEP_PPM_MURTY_AFTER(nv + md) < max_iter) ? PINKHIP_SWEEP_PPM_MURTY_AFTER(nv + md) : max_iter;
   if constexpr (LMP) rare_after = wave_uniform(rare_after);  // (kernel arguments: the same in every lane, and now a scalar)
 
+  if constexpr (SPLIT) {
+    // ---------------------------------------------------------------- the box-only loop in two: exchanges, then closing
+    // The same trips in the same order as the single loop below, which is their commentary: a wave makes ordinary trips
+    // as long as one of its groups runs, and a group that stopped never runs again, so the closing trips follow in a loop of
+    // their own.  Every operation a group sees is the one it saw there -- the zero-factor updates of a group that waits for
+    // its neighbour included (fma(-col, 0, x) decides the sign of a zero).
+    // pivot_on with a predicate in the place of the index (`me`: this lane is lane pi; pvt and sg are read by that lane alone,
+    // rp = 0 is what leaves the rows of a group without a pivot alone).  (defined in here: next to pivot_on, unused, the
+    // lambda changed the device code of the kernels that do not take this branch)
+    auto pivot_lane = [&](bool me, double col, double pvt, double rp, double sg) {
+      double t = col * rp;
+      double cp = col;
+      if (me) {
+        t = 1.0 - sg * rp;
+        cp = pvt - sg;
+      }
+      const BcT xb = bcast_prepare<W>(cp);
+      const double nt = -t;
+      static_for<0, NT>([&](auto Jc) {
+        constexpr int j = decltype(Jc)::value;
+        tset(Jc, fma_bcast<W, j>(tget(Jc), xb, nt));
+      });
+      sdiag_run = fma(cp, nt, sdiag_run);
+      tdiag = me ? -rp : tdiag - t * col;
+    };
+    while (run_m != 0) {
+      ++trips;
+      // (a) the selection
+      const double slo = x - blo, sup = bhi - x;
+      const bool vlo = in && slo < tlo, vup = in && sup < thi;
+      const double viol = vlo ? slo : sup;
+      const float zf = fabsf(static_cast<float>(tdiag));
+      const float wz = (zf > 1e-30f) ? approx_rcpf(zf) : 1e30f;
+      const float fv = static_cast<float>(viol);
+      float key = -(fv * fv) * wz;
+      if (trips > rare_after) {  // (a scalar branch: Murty's least-index rule)
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(key));
+#endif
+        if (it > PINKHIP_SWEEP_PPM_MURTY_AFTER(nv + md)) key = static_cast<float>(li - 64);
+      }
+      const float best32 = group_min32<W>((vlo || vup) ? key32_packf_quiet(key, li | (vlo ? 0 : 64) | ((state != 0) ? 128 : 0)) : 3.0e38f);
+      // a group without a candidate is done; the others take the index from the payload (src stays what it was in a group
+      // that does not exchange: its lane src goes on reading its own diagonal entry as its column entry)
+      run_m &= ~wave_ballot(!(best32 < 0.0f));
+      running = lane_pred(run_m);
+      const int pl = key32_payload(best32);
+      if (running) src = pl & 63;
+      kind = (pl >> 6) & 1;
+      const int nb_src = pl >> 7;
+      if (running) ++it;
+      if (trips > rare_after) {  // (the iteration cap)
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(it));
+#endif
+        const bool over = it > max_iter;
+        if (running && over) status = STATUS_MAX_ITER;
+        run_m &= ~wave_ballot(over);
+        running = lane_pred(run_m);
+      }
+      if (run_m == 0) break;  // (the closing trips of the whole wave start in this very trip)
+      PINKHIP_TICK(3);  // selection
+      // (b) column src
+      // (src is a column in every group, the running mask says whose read counts: no -1 to form, clamp and test)
+      double col;
+      if constexpr (IDX) col = R.template at_group_uniform_on<W>(src, running);
+      else col = column_of(running ? src : -1);
+      if (li == src) col = tdiag;
+      // (c') the exchange
+      const double vs = group_bcast<W>(viol, src);
+      const double num = kind ? vs : -vs;
+      const double pv = group_bcast<W>(tdiag, src);
+      PINKHIP_TICK(4);  // column
+      const double rpv = fast_rcp(pv);
+      const double sgp = nb_src ? 1.0 : -1.0;
+      const unsigned long long bad_m = wave_ballot(!(pv * sgp > 0.0)) & run_m;
+      if (bad_m != 0) {  // (a pivot of the wrong sign: not positive definite on this set)
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(status));
+#endif
+        if (lane_pred(bad_m)) status = STATUS_NOT_PD;
+        run_m &= ~bad_m;
+      }
+      const bool act2 = lane_pred(run_m);
+      const double nu = act2 ? -num * rpv : 0.0;
+      x = fma(-col, nu, x);
+      const bool me = act2 && li == src;
+      if (me) {
+        if (state != 0) {
+          x = ((state == 1) ? lbv : ubv) + nu;
+          state = 0;
+          blo = lbv, bhi = ubv, tlo = thr_lo, thi = thr_up;
+        } else {
+          x = -nu;
+          state = kind + 1;
+          blo = kind ? 0.0 : -INF;
+          bhi = kind ? INF : 0.0;
+          tlo = 0.0, thi = 0.0;
+        }
+      }
+      PINKHIP_TICK(5);
+      PINKHIP_TICK(6);  // exchange
+      pivot_lane(me, col, pv, act2 ? rpv : 0.0, sgp);
+      PINKHIP_TICK(7);  // pivot
+    }
+    PINKHIP_TICK(3);  // (the selection of the trip that ends the exchanges; the closing trips are booked under "exit")
+    // closing trips: the refinement steps and certificates of every group of the wave, at most four
+    if (~ref_m != 0) {
+      refined = lane_pred(ref_m);
+      if (state != 0) x = (state == 1) ? lbv : ubv;  // (from here on x is the point: a fixed coordinate sits on its bound)
+      for (;;) {
+        const bool ref = !refined;
+        bool cert_fails = false;
+        double rres = residual(cert_fails);
+        const double hii_ = (in && state == 0) ? sm[SL::tri(li < NV ? li : 0) + (li < NV ? li : 0)] : 0.0;
+        const double kfin = -group_min<W>(hii_ * tdiag);
+        const bool illc = !(kfin <= PINKHIP_SWEEP_ROUTE_COND);
+        cert_fails = group_first_lane<W>(cert_fails) < W;
+        if (!ref || status != STATUS_OPTIMAL) rres = 0.0;
+        const double sdiag = sdiag_run;
+        const BcT eb = bcast_select<W>(ref, bcast_prepare<W>(rres), bcast_indicator<W>(-1));
+        constexpr int NC = PINKHIP_SWEEP_COLUMN_CHAINS(NT);
+        double c[NC] = {};
+        static_for<0, NT>([&](auto Jc) {
+          constexpr int j = decltype(Jc)::value;
+          c[j % NC] = fma_bcast<W, j>(c[j % NC], eb, tget(Jc));
+        });
+        double col;
+        if constexpr (NC == 4) col = (c[0] + c[1]) + (c[2] + c[3]);
+        else col = c[0] + c[1];
+        const double dbv = (ref && in && state == 0) ? col + (tdiag - sdiag) * rres : 0.0;
+        const double dxv = in ? dbv : 0.0;
+        const double xmax = -group_min<W>(in ? -fabs(x) : 0.0);
+        const bool more = group_first_lane<W>(fabs(dxv) > 1e-9 * fabs(x) + 1e-11 * (1.0 + xmax)) < W;
+        const double dmax = -group_min<W>(-fabs(dxv));
+        const bool sane = dmax <= ((nref == 0) ? 0.1 * xmax : 0.5 * dprev);
+        if (ref) {
+          if (status != STATUS_OPTIMAL || illc) {
+            status_before = status;
+            status = STATUS_BREAKDOWN;
+            PINKHIP_WHY(2);
+            refined = true;
+          } else if (!cert_fails && !more) {
+            if (sane) x += dxv;
+            refined = true;
+          } else if (sane && nref < 3) {
+            x += dxv;
+            dprev = dmax;
+            ++nref;
+          } else {
+            status = STATUS_BREAKDOWN;
+            PINKHIP_WHY(3);
+            refined = true;
+          }
+        }
+        ref_m = wave_ballot(refined);
+        if (~ref_m == 0) break;
+        // (what the single loop's masked-off fall-through does to a group that asks for another step: factors of zero)
+        if (li == src) col = tdiag;
+        x = fma(-col, 0.0, x);
+        pivot_lane(false, col, 1.0, 0.0, -1.0);
+      }
+    }
+  } else
   for (;;) {
     if constexpr (LMP) {
       ++trips;

@@ -12,7 +12,8 @@ strongly connected component of basic blocks that holds the column read with the
 Three reports:
 
   * the loop, block by block, with each block's successors and the part it is counted in;
-  * the ORDINARY TRIP: the blocks of the loop an exchange executes.  The closing trips are the only part of the loop that
+  * the ORDINARY TRIP: the blocks of the loop an exchange executes, with its scalar instructions and, among them, its
+    conditional branches (issue slots: VALU, SALU and branches count together).  The closing trips are the only part of the loop that
     reads LDS (the stated problem, parked there): blocks that read it, blocks that are only reached through them and
     blocks that only lead to them are left out.  A block that a scalar branch jumps around and that holds none of the
     trip's work (no broadcast-FMA, no index read, no permlane swap, a handful of instructions) is counted as RARE: the
@@ -41,7 +42,7 @@ def parse(path):
         m = LABEL.match(l)
         if m or cur is None:
             name = (m.group(1) if m.group(1) else 'bb.' + m.group(2)) if m else 'entry'
-            cur = dict(name=name, line=i + 1, valu=0, dppf=0, salu=0, nop=0, ds=0, scr=0, idx=0, mov64=0, swap=0, ops={}, succ=[], term=False)
+            cur = dict(name=name, line=i + 1, valu=0, dppf=0, salu=0, cbr=0, nop=0, ds=0, scr=0, idx=0, mov64=0, swap=0, ops={}, succ=[], term=False)
             blocks.append(cur)
             if m:
                 continue
@@ -69,6 +70,7 @@ def parse(path):
         elif op.startswith('s_'):
             cur['salu'] += 1
             if op.startswith('s_cbranch'):
+                cur['cbr'] += 1
                 cur['succ'].append(s.split()[1])
             elif op == 's_branch':
                 cur['succ'].append(s.split()[1])
@@ -110,7 +112,7 @@ def short(name):
 def show(b, blocks, tag=''):
     ops = sorted(((n, o) for o, n in b['ops'].items() if o.startswith('v_') and o != 'v_fmac_f64_dpp'), reverse=True)[:6]
     succ = ','.join(short(blocks[t]['name']) for t in b['succ'])
-    print(f"{short(b['name']):8s} L{b['line']:5d} valu {b['valu']:3d} dppfma {b['dppf']:2d} salu {b['salu']:3d} nop {b['nop']:2d} ds {b['ds']:2d} "
+    print(f"{short(b['name']):8s} L{b['line']:5d} valu {b['valu']:3d} dppfma {b['dppf']:2d} salu {b['salu']:3d} cbr {b['cbr']} nop {b['nop']:2d} ds {b['ds']:2d} "
           f"scr {b['scr']} idx {b['idx']} mov64 {b['mov64']:2d} -> {succ:14s} {tag:8s} {ops}")
 
 
@@ -149,9 +151,23 @@ def main():
         show(blocks[n], blocks, 'closing' if n in closing else ('rare' if n in rare else 'trip'))
     t = [blocks[n] for n in trip]
     print(f"\nORDINARY TRIP: {sum(b['valu'] for b in t)} VALU, of which {sum(b['dppf'] for b in t)} broadcast-FMAs and "
-          f"{sum(b['mov64'] for b in t)} v_mov_b64; {sum(b['salu'] for b in t)} SALU, {sum(b['nop'] for b in t)} s_nop, {sum(b['scr'] for b in t)} scratch")
-    print(f"  behind scalar branches a trip jumps around (RARE): {sum(blocks[n]['valu'] for n in rare)} VALU in {len(rare)} blocks")
-    print(f"  closing trips only: {sum(blocks[n]['valu'] for n in closing)} VALU in {len(closing)} blocks")
+          f"{sum(b['mov64'] for b in t)} v_mov_b64; {sum(b['salu'] for b in t)} SALU, of which {sum(b['cbr'] for b in t)} conditional branches; "
+          f"{sum(b['nop'] for b in t)} s_nop, {sum(b['scr'] for b in t)} scratch")
+    print(f"  behind scalar branches a trip jumps around (RARE): {sum(blocks[n]['valu'] for n in rare)} VALU, {sum(blocks[n]['salu'] for n in rare)} SALU "
+          f"in {len(rare)} blocks")
+    print(f"  closing trips only: {sum(blocks[n]['valu'] for n in closing)} VALU, {sum(blocks[n]['salu'] for n in closing)} SALU in {len(closing)} blocks")
+    # the closing trips in a loop of their own (PINKHIP_SWEEP_SPLIT_CLOSING): the first loop behind the tableau loop that reads
+    # LDS and holds a row's worth of broadcast-FMAs
+    if not closing:
+        for n in range(loop[-1] + 1, len(blocks)):
+            if blocks[n]['ds'] and n not in inloop:
+                comp = component_of(blocks, n)
+                if len(comp) > 1 and sum(blocks[m]['dppf'] for m in comp) >= 8:
+                    c = [blocks[m] for m in comp]
+                    print(f"  CLOSING LOOP (separate): {len(comp)} blocks, lines {c[0]['line']} .. {c[-1]['line']}: {sum(b['valu'] for b in c)} VALU, "
+                          f"{sum(b['dppf'] for b in c)} broadcast-FMAs, {sum(b['mov64'] for b in c)} v_mov_b64, {sum(b['salu'] for b in c)} SALU, "
+                          f"{sum(b['scr'] for b in c)} scratch on all paths")
+                    break
     mix = {}
     for b in t:
         for o, c in b['ops'].items():
