@@ -37,6 +37,11 @@ struct EmuModel {
   pinkhip::ModelDev dev;
 };
 
+struct EmuCom {
+  pinkhip::ComImage image;
+  pinkhip::ComDev dev;
+};
+
 // The descriptor part of the kernel arguments, as prepare() of pinkhip.hip fills it: here the tables stay where
 // build_tables put them (`t` must outlive the run)
 int prepare(const pinkhip_desc *d, pinkhip::HostTables &t, KernelArgs &a) {
@@ -166,6 +171,44 @@ int pinkhip_emu_fk_frame_tasks(void *mp, long long B, const double *q, const dou
   a.sE = sE;
   a.sJo = sJ;
   return run_fk(m->dev, B, lane_main_fk_fused<8>, lane_main_fk_fused<32>, lane_main_fk_fused<64>, &a);
+}
+// centre-of-mass rows, mirroring pinkhip_com_create / _com_destroy / _com_task_device on host memory
+int pinkhip_emu_com_create(void *mp, int nj, const double *mass, const double *com, void **out) {
+  if (!mp || !out) return pinkhip::refuse(g_err, PINKHIP_E_INVALID, "null model / out");
+  *out = nullptr;
+  const EmuModel *m = static_cast<const EmuModel *>(mp);
+  EmuCom *c = new EmuCom();
+  const int *parent = reinterpret_cast<const int *>(m->image.bytes.data() + m->image.off_parent);
+  const int rc = pinkhip::build_com_image(m->image.nj, parent, nj, mass, com, c->image, g_err);
+  if (rc) {
+    delete c;
+    return rc;
+  }
+  c->dev = pinkhip::com_view(c->image, c->image.bytes.data());
+  *out = c;
+  return PINKHIP_OK;
+}
+// Test infrastructure: pinkhip_com_create's checks on a tree given as its parent array, without a device model in front of
+// them (a model of more than 64 joints cannot be created: nv <= PINKHIP_MAX_NV)
+int pinkhip_emu_com_image_check(int model_nj, const int *parent, int nj, const double *mass, const double *com) {
+  pinkhip::ComImage im;
+  g_err.clear();
+  return pinkhip::build_com_image(model_nj, parent, nj, mass, com, im, g_err);
+}
+int pinkhip_emu_com_destroy(void *c) {
+  delete static_cast<EmuCom *>(c);
+  return PINKHIP_OK;
+}
+int pinkhip_emu_com_task(void *mp, void *cp, long long B, const double *q, const double *target, int target_batched, double *e,
+                         long long sE, double *J, long long sJ, int row0, double *com_out) {
+  if (!mp || !cp) return pinkhip::refuse(g_err, PINKHIP_E_INVALID, "null handle / model / mass tables");
+  const EmuModel *m = static_cast<const EmuModel *>(mp);
+  const EmuCom *c = static_cast<const EmuCom *>(cp);
+  if (c->image.nj != m->dev.nj) return pinkhip::refuse(g_err, PINKHIP_E_INVALID, "mass tables of another model");
+  pinkhip::ComArgs a{m->dev, c->dev, B, q, target, target_batched, e, J, sE, sJ, row0, com_out};
+  if (const char *bad = pinkhip::com_task_fault(a)) return pinkhip::refuse(g_err, PINKHIP_E_INVALID, bad);
+  if (B == 0) return PINKHIP_OK;
+  return run_fk(m->dev, B, lane_main_com<8>, lane_main_com<32>, lane_main_com<64>, &a);
 }
 int pinkhip_emu_step(void *mp, long long B, const pinkhip_step *st) {
   EmuModel *m = static_cast<EmuModel *>(mp);

@@ -12,6 +12,7 @@
 #include "../pink_amd/csrc/ik_stack_mfma.h"
 #include "../pink_amd/csrc/ik_frame_task.h"
 #include "../pink_amd/csrc/ik_kinematics.h"
+#include "../pink_amd/csrc/ik_com.h"
 #include "../pink_amd/csrc/ik_rollout.h"
 #include "../pink_amd/csrc/model_tables.h"
 #include "../pink_amd/csrc/host_tables.h"
@@ -72,6 +73,11 @@ void lane_main_fk_fused(void *p) {
 template <int W>
 void lane_main_step(void *p) {
   pinkhip::ik_fk_instance<W, true, true>(*static_cast<const pinkhip::FkArgs *>(p), pinkhip::block_id());
+}
+
+template <int W>
+void lane_main_com(void *p) {
+  pinkhip::ik_com_instance<W>(*static_cast<const pinkhip::ComArgs *>(p), pinkhip::block_id());
 }
 
 }  // namespace pinkemu

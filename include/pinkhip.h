@@ -431,6 +431,34 @@ typedef struct pinkhip_sphere_pairs {
 int pinkhip_rollout_step_pairs_device(pinkhip_handle *h, const pinkhip_desc *desc, const pinkhip_model *model,
                                       const pinkhip_rollout_step *args, const pinkhip_sphere_pairs *pairs);
 
+/* ---- ComTask rows (pink/tasks/com_task.py): centre of mass and its Jacobian, formed on the device ----
+ * A pinkhip_com holds the device copy of the mass tables of a model: mass [nj] and com [nj,3], the mass rigidly
+ * attached to every joint and its centre in the joint frame (host pointers, copied at creation), with the subtree
+ * masses and descendant sets derived from the model's tree.  nj must be the model's.
+ *
+ * The task call writes, for every instance b (all per-instance pointers are device pointers),
+ *     e[b sE + row0 + i]            = com_i(q_b) - target_i                      i = 0..2
+ *     J[b sJ + (row0 + i) nv + j]   = d com_i / d (tangent coordinate j)         j = 0..nv-1
+ * and com_out [B,3] when it is not NULL; nothing else in e / J is written.  target is [3], or [B,3] when
+ * target_batched != 0.  Columns follow the library's tangent convention (body twist of a free-flyer): the matrix is
+ * pin.jacobianCenterOfMass.  With sE = K and sJ = Kd nv the rows land in pinkhip_problem.e / .J behind the frame rows
+ * of the fused forward-kinematics call.  That the buffers hold row0 + 3 rows per instance is the caller's business:
+ * only strides too small for them (sE < row0 + 3, sJ < (row0 + 3) nv) are caught.  Enqueued on the handle's current
+ * compute stream, asynchronous.
+ *
+ * Refused, having touched nothing: PINKHIP_E_INVALID for a NULL pointer, an nj that is not the model's, a negative or
+ * non-finite mass, a total mass that is not positive and finite, row0 < 0, such strides; PINKHIP_E_UNSUPPORTED for
+ * nj > 64 (one lane per joint, descendant sets as 64-bit masks; a model of that many joints has nv > PINKHIP_MAX_NV
+ * and is refused when it is created already). */
+#define PINKHIP_HAS_COM_TASK 1
+typedef struct pinkhip_com pinkhip_com;
+int pinkhip_com_create(pinkhip_handle *h, const pinkhip_model *model, int32_t nj, const double *mass,
+                       const double *com, pinkhip_com **out);
+int pinkhip_com_destroy(pinkhip_handle *h, pinkhip_com *com);
+int pinkhip_com_task_device(pinkhip_handle *h, const pinkhip_model *model, const pinkhip_com *com, int64_t B,
+                            const double *q, const double *target, int32_t target_batched, double *e, int64_t sE,
+                            double *J, int64_t sJ, int32_t row0, double *com_out);
+
 /* q [B,nq], q_target [nq] or [B,nq] -> lb, ub [B,nv]; posture error written into e [B,K] at columns
  * e_off .. e_off + nv - root_nv (e may be NULL) */
 int pinkhip_limits_posture_device(pinkhip_handle *h, const pinkhip_model *model, int64_t B, double dt,

@@ -111,6 +111,29 @@ def _relative_frame_task(kin: BatchKinematics, col, solver=None):
     return DenseTaskTerm(J=J, e=e, cost=_costs(col, 6), gain=t0.gain, lm_damping=t0.lm_damping)
 
 
+def com_targets(col: Sequence, B: int) -> np.ndarray:
+    """``[3]`` or ``[B, 3]`` targets of a ComTask slot."""
+    t0 = col[0]
+    if _same(col):
+        if t0.target_coms is not None:
+            if t0.target_coms.shape != (B, 3):
+                raise PinkError(f"ComTask: {t0.target_coms.shape[0]} targets for {B} configurations")
+            return t0.target_coms
+        if t0.target_com is None:
+            raise TargetNotSet("no target set for the centre of mass")
+        return t0.target_com
+    if any(t.target_com is None for t in col):
+        raise TargetNotSet("no target set for the centre of mass")
+    return np.stack([t.target_com for t in col])
+
+
+def _com_task(kin: BatchKinematics, col, solver=None):
+    """``pink/tasks/com_task.py:106-150``: ``e = c(q) - c*``, ``J = jacobianCenterOfMass``."""
+    t0 = col[0]
+    e = kin.center_of_mass() - com_targets(col, kin.B)
+    return DenseTaskTerm(J=kin.jacobian_center_of_mass(), e=e, cost=_costs(col, 3), gain=t0.gain, lm_damping=t0.lm_damping)
+
+
 def _posture_task(kin: BatchKinematics, col, solver=None):
     """``pink/tasks/posture_task.py:100-107``: ``q (-) q*`` on the actuated coordinates."""
     t0, B = col[0], kin.B
@@ -199,12 +222,13 @@ def _fallback_task(kin: BatchKinematics, col, solver=None):
 
 
 def _task_evaluators():
+    from .tasks.com_task import ComTask
     from .tasks.frame_task import FrameTask
     from .tasks.linear_holonomic_task import JointCouplingTask, JointVelocityTask, LinearHolonomicTask
     from .tasks.posture_task import DampingTask, LowAccelerationTask, PostureTask
     from .tasks.relative_frame_task import RelativeFrameTask
 
-    return {FrameTask: _frame_task, RelativeFrameTask: _relative_frame_task, PostureTask: _posture_task,
+    return {ComTask: _com_task, FrameTask: _frame_task, RelativeFrameTask: _relative_frame_task, PostureTask: _posture_task,
             DampingTask: _damping_task, LowAccelerationTask: _low_acceleration_task, JointVelocityTask: _joint_velocity_task,
             LinearHolonomicTask: _linear_holonomic_task, JointCouplingTask: _linear_holonomic_task}
 

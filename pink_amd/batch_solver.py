@@ -409,6 +409,29 @@ class BatchSolver:
         self._check(self._lib.pinkhip_fk_frame_tasks_device(self._h, ctypes.c_void_p(model), B, q, T_target, T_frames,
                                                             e, sE, J, sJ))
 
+    def com_create(self, model: int, mass: np.ndarray, com: np.ndarray) -> int:
+        """Device copy of the mass tables of a device model (``pinkhip_com_create``): ``mass [nj]``, ``com [nj, 3]``
+        (:meth:`pink_amd.configuration.Model.mass_tables`).  ``ValueError`` when the two do not describe the same
+        number of joints; the library refuses a length that is not the model's, a total mass that is not positive and
+        finite (``PinkHipError`` -1) and more than 64 joints (-5)."""
+        mass = np.ascontiguousarray(mass, dtype=np.float64)
+        com = np.ascontiguousarray(com, dtype=np.float64)
+        if mass.ndim != 1 or com.shape != (mass.shape[0], 3):
+            raise ValueError(f"mass [nj] and com [nj, 3] expected, got {mass.shape} and {com.shape}")
+        c = ctypes.c_void_p()
+        self._check(self._lib.pinkhip_com_create(self._h, ctypes.c_void_p(model), mass.shape[0], mass.ctypes.data, com.ctypes.data,
+                                                 ctypes.byref(c)))
+        return c.value
+
+    def com_destroy(self, com: int) -> None:
+        self._check(self._lib.pinkhip_com_destroy(self._h, ctypes.c_void_p(com)))
+
+    def com_task(self, model: int, com: int, B: int, q: int, target: int, target_batched: bool, e: int, sE: int, J: int, sJ: int,
+                 row0: int, com_out=None) -> None:
+        """The three ComTask rows of every instance into ``e`` / ``J`` at row ``row0`` (``pinkhip_com_task_device``)."""
+        self._check(self._lib.pinkhip_com_task_device(self._h, ctypes.c_void_p(model), ctypes.c_void_p(com), B, q, target,
+                                                      int(bool(target_batched)), e, sE, J, sJ, int(row0), com_out))
+
     def step_kernel(self, model: int, B: int, args) -> None:
         """Whole control step around the solve in one launch (``pinkhip_step_device``)."""
         self._check(self._lib.pinkhip_step_device(self._h, ctypes.c_void_p(model), B, ctypes.byref(args)))

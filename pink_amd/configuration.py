@@ -75,6 +75,8 @@ class Joint:
     nq: int
     idx_v: int
     nv: int
+    mass: float = 0.0  # everything rigidly attached to the joint
+    com: Optional[np.ndarray] = None  # its centre, in the joint frame
 
 
 @dataclass
@@ -98,8 +100,15 @@ class Model:
 
     # -- construction ---------------------------------------------------------
     def add_joint(self, name: str, kind: str, parent: int = -1, placement: Optional[SE3] = None,
-                  axis=None, lower: float = -np.inf, upper: float = np.inf, velocity: float = np.inf) -> int:
+                  axis=None, lower: float = -np.inf, upper: float = np.inf, velocity: float = np.inf,
+                  mass: float = 0.0, com=None) -> int:
+        """``mass``, ``com``: the mass rigidly attached to the joint and its centre in the joint frame (what
+        ``pin.Model.inertias[j]`` carries for ``pin.centerOfMass``; inertia tensors are not read)."""
         placement = SE3() if placement is None else placement
+        mass = float(mass)
+        if not (mass >= 0.0 and np.isfinite(mass)):
+            raise ValueError(f"mass of joint {name!r} must be finite and not negative, got {mass}")
+        com = np.zeros(3) if com is None else np.array(com, dtype=float).reshape(3)
         if kind == "free_flyer":
             nq, nv = 7, 6
             lo, up, vel = [-np.inf] * 7, [np.inf] * 7, [np.inf] * 6
@@ -110,7 +119,7 @@ class Model:
             axis = axis / np.linalg.norm(axis)
         else:
             raise ValueError(kind)
-        self.joints.append(Joint(name, kind, parent, placement, axis, self.nq, nq, self.nv, nv))
+        self.joints.append(Joint(name, kind, parent, placement, axis, self.nq, nq, self.nv, nv, mass, com))
         self.nq += nq
         self.nv += nv
         self._lower += lo
@@ -122,6 +131,42 @@ class Model:
 
     def add_frame(self, name: str, joint: int, placement: Optional[SE3] = None) -> None:
         self.frames.append(Frame(name, joint, SE3() if placement is None else placement))
+
+    def add_mass(self, joint: int, mass: float, com) -> None:
+        """Attach another rigid body to ``joint`` (``com`` in the joint frame): masses add, centres combine mass-weighted
+        (what Pinocchio's ``appendBodyToJoint`` does with the inertias of links behind fixed joints).  ``joint = -1``,
+        the world, is ignored: mass fixed to the world does not move (``pin.centerOfMass`` starts at joint 1)."""
+        mass = float(mass)
+        if not (mass >= 0.0 and np.isfinite(mass)):
+            raise ValueError(f"mass must be finite and not negative, got {mass}")
+        if joint < 0 or mass == 0.0:
+            return
+        j = self.joints[joint]
+        total = j.mass + mass
+        j.com = (j.mass * j.com + mass * np.asarray(com, dtype=float).reshape(3)) / total
+        j.mass = total
+
+    @property
+    def total_mass(self) -> float:
+        return float(sum(j.mass for j in self.joints))
+
+    def mass_tables(self) -> Tuple[np.ndarray, np.ndarray]:
+        """``(mass [nj], com [nj, 3])`` of the joints."""
+        return (np.array([j.mass for j in self.joints], dtype=np.float64),
+                np.array([j.com for j in self.joints], dtype=np.float64).reshape(len(self.joints), 3))
+
+    def subtree_tables(self) -> Tuple[np.ndarray, np.ndarray]:
+        """``(subtree_mass [nj], descendant [nj, nj] bool)``: ``descendant[a, k]`` says that joint ``k`` is ``a`` or
+        behind it -- the joints a motion of ``a`` carries along."""
+        nj = len(self.joints)
+        sub = np.array([j.mass for j in self.joints], dtype=np.float64)
+        desc = np.eye(nj, dtype=bool)
+        for k in range(nj - 1, -1, -1):  # (topological order: parent < child)
+            p = self.joints[k].parent
+            if p >= 0:
+                sub[p] += sub[k]
+                desc[p] |= desc[k]
+        return sub, desc
 
     def ensure_limits(self) -> "Model":
         """The model's default limits and tangent space, attached on first use (``pink/configuration.py:101-108``
@@ -306,6 +351,51 @@ class Configuration:
         R = self.oMi[joint].rotation
         return np.vstack([R @ J[:3], R @ J[3:]])
 
+    def center_of_mass(self) -> np.ndarray:
+        """World position of the centre of mass, ``[3]`` (``pin.centerOfMass``)."""
+        m = self.model
+        M = m.total_mass
+        if not M > 0.0:
+            raise ValueError("the model carries no mass: its centre of mass is undefined")
+        c = np.zeros(3)
+        for j, T in zip(m.joints, self.oMi):
+            if j.mass != 0.0:
+                c += j.mass * (T.rotation @ j.com + T.translation)
+        return c / M
+
+    def jacobian_center_of_mass(self) -> np.ndarray:
+        """``[3, nv]``: velocity of the centre of mass in the world per unit tangent velocity (``pin.jacobianCenterOfMass``;
+        the free-flyer's columns are those of its body twist).  A joint moves the centre of mass of its subtree:
+        ``axis x (c_sub - p) M_sub / M`` for a rotation about an axis through ``p``, ``axis M_sub / M`` for a
+        translation."""
+        m = self.model
+        M = m.total_mass
+        if not M > 0.0:
+            raise ValueError("the model carries no mass: its centre of mass is undefined")
+        nj = len(m.joints)
+        s = np.zeros((nj, 3))  # first moment of the subtree of every joint
+        sub = np.zeros(nj)
+        for k in range(nj - 1, -1, -1):
+            j, T = m.joints[k], self.oMi[k]
+            if j.mass != 0.0:
+                s[k] += j.mass * (T.rotation @ j.com + T.translation)
+            sub[k] += j.mass
+            if j.parent >= 0:
+                s[j.parent] += s[k]
+                sub[j.parent] += sub[k]
+        J = np.zeros((3, m.nv))
+        for k, j in enumerate(m.joints):
+            R, p = self.oMi[k].rotation, self.oMi[k].translation
+            r = (s[k] - sub[k] * p) / M
+            if j.kind == "revolute":
+                J[:, j.idx_v] = np.cross(R @ j.axis, r)
+            elif j.kind == "prismatic":
+                J[:, j.idx_v] = (R @ j.axis) * (sub[k] / M)
+            else:
+                J[:, j.idx_v:j.idx_v + 3] = R * (sub[k] / M)
+                J[:, j.idx_v + 3:j.idx_v + 6] = np.cross(R.T, r).T  # column i: (R e_i) x r
+        return J
+
     def get_transform_frame_to_world(self, frame: str) -> SE3:
         return self.oMf[self.model.getFrameId(frame)].copy()
 
@@ -390,6 +480,21 @@ def load_urdf(path: str, free_flyer: bool = False) -> Model:
     model = Model()
     base_joint = model.add_joint("root_joint", "free_flyer") if free_flyer else -1
     model.add_frame(base, base_joint, SE3())
+    link_elems = {l.get("name"): l for l in root.findall("link")}
+
+    def attach(link: str, joint_idx: int, offset: SE3) -> None:
+        """``<inertial>`` of ``link`` onto joint ``joint_idx``, ``offset`` being the link frame in the joint frame: links
+        behind fixed joints fold into their moving parent, mass fixed to the world does not count."""
+        el = link_elems.get(link)
+        inertial = el.find("inertial") if el is not None else None
+        mass_el = inertial.find("mass") if inertial is not None else None
+        if mass_el is None:
+            return
+        o = inertial.find("origin")
+        xyz = [float(v) for v in (o.get("xyz", "0 0 0") if o is not None else "0 0 0").split()]
+        model.add_mass(joint_idx, float(mass_el.get("value", "0")), offset.rotation @ np.array(xyz) + offset.translation)
+
+    attach(base, base_joint, SE3())
 
     def walk(link: str, joint_idx: int, offset: SE3) -> None:
         for j in children.get(link, []):
@@ -401,6 +506,7 @@ def load_urdf(path: str, free_flyer: bool = False) -> Model:
             child = j.find("child").get("link")
             if kind == "fixed":
                 model.add_frame(child, joint_idx, T)
+                attach(child, joint_idx, T)
                 walk(child, joint_idx, T)
                 continue
             ax = j.find("axis")
@@ -412,6 +518,7 @@ def load_urdf(path: str, free_flyer: bool = False) -> Model:
             idx = model.add_joint(j.get("name"), "prismatic" if kind == "prismatic" else "revolute", joint_idx, T,
                                   axis, lo, up, vel)
             model.add_frame(child, idx, SE3())
+            attach(child, idx, SE3())
             walk(child, idx, SE3())
 
     walk(base, base_joint, SE3())
@@ -419,9 +526,10 @@ def load_urdf(path: str, free_flyer: bool = False) -> Model:
 
 
 def build_chain(n: int, link_length: float = 0.3, free_flyer: bool = False, seed: int = 0,
-                limit: float = np.pi, velocity: float = 3.15) -> Model:
+                limit: float = np.pi, velocity: float = 3.15, mass_seed: Optional[int] = None) -> Model:
     """A serial arm of ``n`` revolute joints with varied axes (UR-like when ``n = 6``),
-    tool frame ``"tool0"`` at the tip."""
+    tool frame ``"tool0"`` at the tip.  ``mass_seed``: draw a mass and a centre for every joint (a generator of its own:
+    the kinematics do not depend on it); the default stays massless."""
     rng = np.random.default_rng(seed)
     model = Model()
     parent = model.add_joint("root_joint", "free_flyer") if free_flyer else -1
@@ -431,4 +539,16 @@ def build_chain(n: int, link_length: float = 0.3, free_flyer: bool = False, seed
         off = SE3(np.eye(3), [0.0, 0.0, 0.1] if i == 0 else [link_length * (0.5 + 0.5 * ((i + 1) % 2)), 0.0, 0.05 * (i % 3)])
         parent = model.add_joint(f"joint_{i + 1}", "revolute", parent, off, axis, -limit, limit, velocity)
     model.add_frame("tool0", parent, SE3(np.eye(3), [link_length * 0.5, 0.0, 0.0]))
+    if mass_seed is not None:
+        draw_masses(model, mass_seed)
+    return model
+
+
+def draw_masses(model: Model, seed: int, scale: float = 0.1) -> Model:
+    """Seeded masses (0.5 .. 5 kg) and centres (``scale`` metres off the joint origin, off the joint axis) for every
+    joint of ``model``, in place."""
+    rng = np.random.default_rng(seed)
+    for j in model.joints:
+        j.mass = float(rng.uniform(0.5, 5.0))
+        j.com = scale * rng.normal(size=3)
     return model

@@ -20,6 +20,7 @@
 #include "ik_stack_mfma.h"
 #include "ik_frame_task.h"
 #include "ik_kinematics.h"
+#include "ik_com.h"
 #include "ik_rollout.h"
 #include "host_tables.h"
 #include "model_tables.h"
@@ -38,6 +39,12 @@ struct pinkhip_model {
   pinkhip::ModelImage image;
   char *d_base = nullptr;
   pinkhip::ModelDev dev;
+};
+
+struct pinkhip_com {
+  pinkhip::ComImage image;
+  char *d_base = nullptr;
+  pinkhip::ComDev dev;
 };
 
 struct pinkhip_handle {
@@ -662,6 +669,66 @@ int pinkhip_fk_frame_tasks_device(pinkhip_handle *h, const pinkhip_model *m, int
     hipLaunchKernelGGL(pinkhip::ik_fk_frame_tasks_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
   } else {
     hipLaunchKernelGGL(pinkhip::ik_fk_frame_tasks_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
+  }
+  PH_HIP(h, hipGetLastError());
+  return PINKHIP_OK;
+}
+
+int pinkhip_com_create(pinkhip_handle *h, const pinkhip_model *m, int32_t nj, const double *mass, const double *com,
+                       pinkhip_com **out) {
+  if (!h || !m || !out) return fail(h, PINKHIP_E_INVALID, "null handle / model / out");
+  *out = nullptr;
+  pinkhip_com *c = new (std::nothrow) pinkhip_com();
+  if (!c) return fail(h, PINKHIP_E_NOMEM, "out of host memory");
+  std::string why;
+  const int *parent = reinterpret_cast<const int *>(m->image.bytes.data() + m->image.off_parent);
+  const int rc = pinkhip::build_com_image(m->image.nj, parent, nj, mass, com, c->image, why);
+  if (rc) {
+    delete c;
+    return fail(h, rc, why);
+  }
+  hipError_t e = hipSetDevice(h->device);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->d_base), c->image.bytes.size());
+  if (e == hipSuccess) e = hipMemcpy(c->d_base, c->image.bytes.data(), c->image.bytes.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (c->d_base) (void)hipFree(c->d_base);
+    delete c;
+    return fail(h, PINKHIP_E_HIP, std::string("pinkhip_com_create: ") + hipGetErrorString(e));
+  }
+  c->dev = pinkhip::com_view(c->image, c->d_base);
+  *out = c;
+  return PINKHIP_OK;
+}
+
+int pinkhip_com_destroy(pinkhip_handle *h, pinkhip_com *c) {
+  if (!c) return PINKHIP_OK;
+  if (h) {
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+  }
+  if (c->d_base) (void)hipFree(c->d_base);
+  delete c;
+  return PINKHIP_OK;
+}
+
+int pinkhip_com_task_device(pinkhip_handle *h, const pinkhip_model *m, const pinkhip_com *c, int64_t B, const double *q,
+                            const double *target, int32_t target_batched, double *e, int64_t sE, double *J, int64_t sJ,
+                            int32_t row0, double *com_out) {
+  if (!h || !m || !c) return fail(h, PINKHIP_E_INVALID, "null handle / model / mass tables");
+  if (c->image.nj != m->dev.nj) return fail(h, PINKHIP_E_INVALID, "mass tables of another model");
+  const pinkhip::ComArgs a{m->dev, c->dev, B, q, target, target_batched, e, J, sE, sJ, row0, com_out};
+  if (const char *bad = pinkhip::com_task_fault(a)) return fail(h, PINKHIP_E_INVALID, bad);
+  if (B == 0) return PINKHIP_OK;
+  PH_HIP(h, hipSetDevice(h->device));
+  const int per = pinkhip::com_lds_doubles(m->dev.nj);
+  const dim3 block(pinkhip::kWave);
+  const int width = m->dev.nv > m->dev.nj ? m->dev.nv : m->dev.nj;  // lanes per instance: one per joint / column
+  if (width <= 8) {
+    hipLaunchKernelGGL(pinkhip::ik_com_task_kernel<8>, dim3((unsigned)((B + 7) / 8)), block, 8 * 8 * per + 16, h->stream, a);
+  } else if (width <= 32) {
+    hipLaunchKernelGGL(pinkhip::ik_com_task_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
+  } else {
+    hipLaunchKernelGGL(pinkhip::ik_com_task_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
   }
   PH_HIP(h, hipGetLastError());
   return PINKHIP_OK;

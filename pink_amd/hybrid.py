@@ -30,8 +30,10 @@ MAX_FRAME_TASKS = 16
 
 def plan(kin_model, slots: Sequence, constraints) -> Optional[List[int]]:
     """Indices of the FrameTask slots when the hybrid route serves this stack, else ``None``: at least one FrameTask,
-    every other task of a class whose batched evaluator yields a diagonal term; equality constraints (slots of
-    ``constraints=``) made of FrameTasks / RelativeFrameTasks."""
+    at most one ComTask on a model that carries mass (two or more: the host evaluates them), every other task of a
+    class whose batched evaluator yields a diagonal term; equality constraints (slots of ``constraints=``) made of
+    FrameTasks / RelativeFrameTasks."""
+    from .tasks.com_task import ComTask
     from .tasks.frame_task import FrameTask
     from .tasks.linear_holonomic_task import JointVelocityTask
     from .tasks.posture_task import DampingTask, LowAccelerationTask, PostureTask
@@ -58,10 +60,20 @@ def plan(kin_model, slots: Sequence, constraints) -> Optional[List[int]]:
             return None
     if not frames or len(frames) > MAX_FRAME_TASKS:
         return None
+    coms = [k for k, col in enumerate(slots) if type(col[0]) is ComTask]
+    if len(coms) > 1 or (coms and not (kin_model.total_mass > 0.0 and len(kin_model.joints) <= 64)):
+        return None
     for k, col in enumerate(slots):
-        if k not in frames and type(col[0]) not in (PostureTask, DampingTask, LowAccelerationTask, JointVelocityTask):
+        if k not in frames and k not in coms and type(col[0]) not in (PostureTask, DampingTask, LowAccelerationTask, JointVelocityTask):
             return None
     return frames
+
+
+def com_slot(slots: Sequence) -> Optional[int]:
+    """Index of the ComTask slot of a stack :func:`plan` accepted, or ``None``."""
+    from .tasks.com_task import ComTask
+
+    return next((k for k, col in enumerate(slots) if type(col[0]) is ComTask), None)
 
 
 class HybridState:
@@ -76,6 +88,19 @@ class HybridState:
         self.dmodel = api.model_create(self.arrays.desc)
         self.bufs = {}
         self.cframes, self.carrays, self.cmodel = None, None, None  # device model of the equality constraints' frames
+        self.dcom, self.com_key = None, None  # device copy of the model's mass tables (a ComTask slot)
+
+    def com_tables(self) -> int:
+        """The device mass tables of the model as it is NOW (an edit of a mass or a centre builds them anew)."""
+        mass, com = self.model.mass_tables()
+        key = (mass.tobytes(), com.tobytes())
+        if self.com_key != key:
+            if self.dcom is not None:
+                self.api.com_destroy(self.dcom)
+                self.dcom = None
+            self.dcom = self.api.com_create(self.dmodel, mass, com)
+            self.com_key = key
+        return self.dcom
 
     def constraint_model(self, frames) -> int:
         frames = tuple(frames)
@@ -105,6 +130,9 @@ class HybridState:
         if self.cmodel is not None:
             self.api.model_destroy(self.cmodel)
             self.cmodel = None
+        if self.dcom is not None:
+            self.api.com_destroy(self.dcom)
+            self.dcom = None
         self.api.model_destroy(self.dmodel)
 
 
@@ -117,7 +145,10 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     nv, nq, nf = model.nv, model.nq, len(frame_slots)
     kq = _QOnly(model, kin_q, kin)
     # diagonal tasks, limits, barriers: host (vectorised, pink_amd/batch_eval.py)
-    diag = [be.task_term(kq, col, None) for k, col in enumerate(slots) if k not in frame_slots]
+    kc = com_slot(slots)
+    ccol = None if kc is None else slots[kc]
+    nc = 0 if ccol is None else 1
+    diag = [be.task_term(kq, col, None) for k, col in enumerate(slots) if k not in frame_slots and k != kc]
     if any(not isinstance(t, DiagonalTaskTerm) for t in diag):
         raise PinkError("hybrid route: a task outside the FrameTasks produced a dense Jacobian")
     lb = np.full((B, nv), -np.inf)
@@ -139,29 +170,38 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     fcols = [slots[k] for k in frame_slots]
     for col in fcols:  # (gain / lm_damping are read off the first task of a slot: the same refusal as the host route)
         be._check_slot(col)
-    Kd, K = 6 * nf, 6 * nf + b0.K
+    # ... and the ComTask's: one dense task of three rows behind them
+    if ccol is not None:
+        be._check_slot(ccol)
+        ctarget = np.ascontiguousarray(be.com_targets(ccol, B), dtype=np.float64)
+    Kd = 6 * nf + 3 * nc
+    K = Kd + b0.K
     fcost = [be._costs(col, 6) for col in fcols]
+    widths = [6] * nf + [3] * nc
+    if ccol is not None:
+        fcost.append(be._costs(ccol, 3))
+        fcols = fcols + [ccol]
     batched = b0.cost.ndim == 2 or any(np.ndim(c) == 2 for c in fcost)
     if batched:
-        cost = np.concatenate([np.broadcast_to(np.asarray(c, dtype=float), (B, 6)) for c in fcost]
+        cost = np.concatenate([np.broadcast_to(np.asarray(c, dtype=float), (B, w)) for c, w in zip(fcost, widths)]
                               + [np.broadcast_to(b0.cost, (B, b0.K))], axis=1)
     else:
-        cost = np.concatenate([np.broadcast_to(np.asarray(c, dtype=float), (6,)) for c in fcost] + [b0.cost])
+        cost = np.concatenate([np.broadcast_to(np.asarray(c, dtype=float), (w,)) for c, w in zip(fcost, widths)] + [b0.cost])
     cost = np.ascontiguousarray(cost)
     e_full = np.zeros((B, K))  # (the kernel overwrites the FrameTask rows: one contiguous upload instead of a strided one)
     e_full[:, Kd:] = b0.e
     # (a RelativeFrameTask's target lives in its root frame: a relative slot of the device model, include/pinkhip.h)
-    targets = np.ascontiguousarray(np.stack([_targets_of(col, B) for col in fcols], axis=1))  # [B, nf, 12]
+    targets = np.ascontiguousarray(np.stack([_targets_of(col, B) for col in fcols[:nf]], axis=1))  # [B, nf, 12]
     i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)  # noqa: E731
     f64 = lambda v: np.ascontiguousarray(v, dtype=np.float64)  # noqa: E731
-    task_rows = i32([6 * i for i in range(nf + 1)] + [Kd + int(r) for r in b0.task_rows[1:]])
-    task_kind = i32([0] * nf + list(b0.task_kind))
-    task_col0 = i32([0] * nf + list(b0.task_col0))
+    task_rows = i32([6 * i for i in range(nf + 1)] + [Kd] * nc + [Kd + int(r) for r in b0.task_rows[1:]])
+    task_kind = i32([0] * (nf + nc) + list(b0.task_kind))
+    task_col0 = i32([0] * (nf + nc) + list(b0.task_col0))
     gain = f64([col[0].gain for col in fcols] + list(b0.gain))
     lm = f64([col[0].lm_damping for col in fcols] + list(b0.lm_damping))
     brow, bsafe = i32(b0.barrier_rows), f64(b0.barrier_safe_gain if b0.barrier_safe_gain.size else [0.0])
     d = Desc()
-    d.B, d.nv, d.T, d.Kd, d.K, d.md, d.n_eq = B, nv, nf + len(diag), Kd, K, b0.md, n_eq
+    d.B, d.nv, d.T, d.Kd, d.K, d.md, d.n_eq = B, nv, nf + nc + len(diag), Kd, K, b0.md, n_eq
     d.task_rows, d.task_kind, d.task_col0 = (a.ctypes.data_as(c_int32_p) for a in (task_rows, task_kind, task_col0))
     d.gain, d.lm_damping = gain.ctypes.data_as(c_double_p), lm.ctypes.data_as(c_double_p)
     d.n_barriers = int(b0.barrier_safe_gain.size)
@@ -190,6 +230,10 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
         p.c_extra = s.buf("c_extra", b0.c_extra.nbytes)
         api.put(p.c_extra, b0.c_extra)
     api.fk_frame_tasks(s.dmodel, B, d_q, d_Tt, None, d_e, K, d_J, Kd * nv)
+    if ccol is not None:  # the three ComTask rows behind the frame rows of the same streams
+        d_ct = s.buf("com_target", ctarget.nbytes)
+        api.put(d_ct, ctarget)
+        api.com_task(s.dmodel, s.com_tables(), B, d_q, d_ct, ctarget.ndim == 2, d_e, K, d_J, Kd * nv, 6 * nf)
     if n_eq:
         # the same kernel on the constraints' frames, writing J into the leading rows of Gd and e into those of hd (row
         # pitches md nv and md); hd then becomes -gain e on the host: [B, md] doubles go home and back

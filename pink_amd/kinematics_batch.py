@@ -164,6 +164,43 @@ class BatchKinematics:
         """``pin.getJointJacobian(..., LOCAL_WORLD_ALIGNED)`` of joint ``joint``: ``[B, 6, nv]``."""
         return self._jacobian_at(self.R[:, joint], self.p[:, joint], joint, rotate=False)
 
+    # -- pin.centerOfMass / pin.jacobianCenterOfMass over the batch ----------------------------------------
+    def _moments(self) -> np.ndarray:
+        """``[B, nj, 3]``: first moment ``m_k x_k`` of the mass attached to every joint."""
+        mass, com = self.model.mass_tables()
+        if not mass.sum() > 0.0:
+            raise ValueError("the model carries no mass: its centre of mass is undefined")
+        x = np.einsum("bkij,kj->bki", self.R, com) + self.p
+        return np.where(mass[None, :, None] != 0.0, mass[None, :, None] * x, 0.0)
+
+    def center_of_mass(self) -> np.ndarray:
+        """``[B, 3]``: world position of the centre of mass (``Configuration.center_of_mass``)."""
+        return self._moments().sum(axis=1) / self.model.total_mass
+
+    def jacobian_center_of_mass(self) -> np.ndarray:
+        """``[B, 3, nv]`` (``Configuration.jacobian_center_of_mass``): a joint moves the centre of mass of its
+        subtree."""
+        m, B = self.model, self.B
+        M = m.total_mass
+        sub, desc = m.subtree_tables()
+        s = np.einsum("ak,bki->bai", desc.astype(np.float64), self._moments())  # first moment of every subtree
+        r = (s - sub[None, :, None] * self.p) / M  # [B, nj, 3]
+        aw = self._axes_world()
+        J = np.zeros((B, 3, m.nv))
+        rev = [k for k, j in enumerate(m.joints) if j.kind == "revolute"]
+        pri = [k for k, j in enumerate(m.joints) if j.kind == "prismatic"]
+        if rev:
+            J[:, :, [m.joints[k].idx_v for k in rev]] = np.swapaxes(np.cross(aw[:, rev], r[:, rev]), 1, 2)
+        if pri:
+            J[:, :, [m.joints[k].idx_v for k in pri]] = np.swapaxes(aw[:, pri] * (sub[pri] / M)[None, :, None], 1, 2)
+        for k, j in enumerate(m.joints):
+            if j.kind == "free_flyer":
+                Rk = self.R[:, k]
+                J[:, :, j.idx_v:j.idx_v + 3] = Rk * (sub[k] / M)
+                # column i: (R e_i) x r
+                J[:, :, j.idx_v + 3:j.idx_v + 6] = np.swapaxes(np.cross(np.swapaxes(Rk, 1, 2), r[:, k, None, :]), 1, 2)
+        return J
+
     # -- pin.difference / pin.dDifference over the batch --------------------------------------------------
     def _free_flyer_pose(self, j, q: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         q = np.broadcast_to(q, (self.B, self.model.nq)) if q.ndim == 1 else q

@@ -191,8 +191,17 @@ class DeviceRollout:
                  fused: bool = True, safety_break: bool = True, posture_lm_damping: float = 0.0,
                  position_barriers: Sequence = (), floating_base_limit=None, const_tasks: Sequence = (),
                  diag_tasks: Sequence = (), acceleration_limit: Optional[np.ndarray] = None,
-                 velocity_limit: Optional[np.ndarray] = None, constraint_slots: Sequence = (), warm_start: bool = False):
-        """``warm_start``: every step starts its QP solver from the active set the previous step of the same robot ended
+                 velocity_limit: Optional[np.ndarray] = None, constraint_slots: Sequence = (), warm_start: bool = False,
+                 com_task=None):
+        """``com_task``: a :class:`pink_amd.tasks.ComTask` (``pink/tasks/com_task.py``) whose three rows
+        ``pinkhip_com_task_device`` forms behind the FrameTask rows, from the configuration the step solves at and the
+        model's mass tables (``fused=True``: step kernel, centre-of-mass kernel, solve; ``fused=False``: one more launch in
+        front of the solve).  The whole-step kernel does not form centre-of-mass rows: ``fused="kernel"`` raises.  The target
+        is the task's (one for all robots, or ``[B, 3]``) until :meth:`set_com_target` replaces it.  The model's mass tables
+        are copied to the device ONCE, here: an edit of ``Joint.mass`` / ``Joint.com`` afterwards is not seen by this rollout
+        (build a new one; :func:`pink_amd.solve_ik_batch` on the hybrid route compares the tables with every call).
+
+        ``warm_start``: every step starts its QP solver from the active set the previous step of the same robot ended
         on (the joints saturated at step t are mostly those saturated at step t + 1: fewer sweeps, fewer exchanges, the
         same minimiser -- ``include/pinkhip.h``, ``pinkhip_warm``).  Needs the whole-step kernel (``fused="kernel"``) and a
         box-only stack; see :meth:`last_active` / :meth:`set_active`.
@@ -225,6 +234,16 @@ class DeviceRollout:
                              'no equality constraints, no dense floating-base limit rows')
         self.B = B = int(q0.shape[0])
         self.nv, self.nq = model.nv, model.nq
+        self.com_task, self.dcom, self.d_com, self.d_com_target = com_task, None, None, None
+        if com_task is not None:
+            if self.fused == "kernel":
+                raise ValueError('the whole-step kernel does not form centre-of-mass rows: a ComTask needs fused=True or fused=False')
+            if not hasattr(api, "com_task"):
+                raise ValueError("this solver has no pinkhip_com_task_device: a ComTask needs it")
+            if not model.total_mass > 0.0:
+                raise ValueError("the model carries no mass: its centre of mass is undefined")
+            if len(model.joints) > 64:
+                raise ValueError("centre-of-mass rows on the device need a model of at most 64 joints")
         # (a frame task (frame, ...) regulates the frame in the world; ((frame, root), ...) the pose of frame in root --
         # a RelativeFrameTask, pink/tasks/relative_frame_task.py: a relative slot of the device model)
         self.arrays = ModelArrays(model, [ft[0] for ft in frame_tasks], velocity_limit=velocity_limit)
@@ -251,7 +270,8 @@ class DeviceRollout:
             raise ValueError("constant-row tasks: A must be [k, nv] and q_0 [nq]")
         if self.n_crow and any(not np.array_equal(q_0, const_tasks[0][2]) for _, _, q_0, *_ in const_tasks):
             raise ValueError("constant-row tasks must share one reference configuration q_0")
-        self.Kd = 6 * nf + self.n_crow
+        self.n_com = 3 if com_task is not None else 0
+        self.Kd = 6 * nf + self.n_crow + self.n_com  # (n_crow = 0 beside a ComTask: constant-row tasks need fused="kernel")
         n_post = nv - root_nv if posture_cost is not None else 0
         self.K = self.Kd + n_post + sum(e.shape[0] for _, e, *_ in diag_tasks)
         # task tables of the QP (include/pinkhip.h: frame tasks, constant-row tasks, then the diagonal ones: the posture first)
@@ -263,6 +283,9 @@ class DeviceRollout:
             k = A.shape[0]
             rows.append(rows[-1] + k), kind.append(0), col0.append(0), gain.append(g), lm.append(l)
             cost += list(np.broadcast_to(np.ones(k) if c is None else np.asarray(c, float), (k,)))
+        if com_task is not None:  # three dense rows behind the frame rows
+            rows.append(rows[-1] + 3), kind.append(0), col0.append(0), gain.append(float(com_task.gain)), lm.append(float(com_task.lm_damping))
+            cost += list(np.broadcast_to(np.asarray(com_task.cost, float), (3,)))
         if n_post:
             rows.append(rows[-1] + n_post), kind.append(1), col0.append(root_nv), gain.append(posture_gain), lm.append(posture_lm_damping)
             cost += [float(posture_cost)] * n_post
@@ -398,6 +421,12 @@ class DeviceRollout:
         a.put(self.d_fail, np.zeros(B, dtype=np.int32))
         self._fail_dirty = False
         self.d_qt = f8(B, nq)
+        if com_task is not None:
+            from . import batch_eval as be
+
+            self.dcom = a.com_create(self.dmodel, *model.mass_tables())
+            self.d_com, self.d_com_target = f8(B, 3), f8(B, 3)
+            self.set_com_target(be.com_targets([com_task], B))
         if self.warm_start:  # one byte per robot and tangent coordinate, read and written in place by every step
             self.d_active = a.alloc(B * nv)
             a.put(self.d_active, np.zeros(B * nv, dtype=np.uint8))
@@ -602,6 +631,32 @@ class DeviceRollout:
             self.d_Tq = self.api.alloc(8 * 7 * self.B * max(len(self.frames), 1))
         return self.d_Tq + 8 * 7 * (self.B * f + lo)
 
+    def set_com_target(self, target) -> None:
+        """Target of the ComTask from the next step on: ``[3]`` for every robot, or ``[B, 3]``."""
+        if self.com_task is None:
+            raise ValueError("this rollout has no ComTask")
+        t = np.ascontiguousarray(target, dtype=np.float64)
+        if t.shape not in ((3,), (self.B, 3)):
+            raise ValueError(f"the centre-of-mass target must have shape (3,) or {(self.B, 3)}, got {t.shape}")
+        self.com_batched = t.ndim == 2
+        self.api.put(self.d_com_target, t)
+
+    def _com_rows(self) -> None:
+        """The ComTask rows (and the centres themselves) of the configurations in ``d_q``, behind the frame rows."""
+        self.api.com_task(self.dmodel, self.dcom, self.B, self.d_q, self.d_com_target, self.com_batched, self.d_e, self.K,
+                          self.d_J, self.Kd * self.nv, 6 * len(self.frames), self.d_com)
+
+    def center_of_mass(self) -> np.ndarray:
+        """``[B, 3]``: centres of mass of the current configurations, computed on the device."""
+        if self.com_task is None:
+            raise ValueError("this rollout has no ComTask")
+        self.flush()
+        self._com_rows()  # (the rows it writes are formed anew by every step)
+        self.api.sync()
+        c = np.zeros((self.B, 3))
+        self.api.get(c, self.d_com)
+        return c
+
     def step(self, integrate: bool = True) -> None:
         """Enqueue one IK step for every robot (asynchronous).  ``integrate=False`` only solves (dq, status and
         iteration counts of ``last_step`` are those of the current configurations, which stay as they are)."""
@@ -638,6 +693,8 @@ class DeviceRollout:
             st.lb, st.ub, st.e_off = self.d_lb, self.d_ub, self.Kd
             st.root_box = self.d_lim[0] if self.d_lim else None
             a.step_kernel(self.dmodel, B, st)
+            if self.com_task is not None:  # (the step kernel has advanced q already)
+                self._com_rows()
             a.solve_raw(self.desc, self.problem, self.result)
             self._pending = bool(integrate)
         else:  # one launch for FK, one per FrameTask, limits + posture, solve, integrate
@@ -648,6 +705,8 @@ class DeviceRollout:
                                      self.d_J + 8 * 6 * nv * t, self.Kd * nv)
             a.limits_posture(self.dmodel, B, self.dt, self.config_limit_gain, self.d_q, self.d_qt, self.qt_batched, self.d_lb, self.d_ub,
                              self.d_e if self.n_post else None, self.K, self.Kd)
+            if self.com_task is not None:
+                self._com_rows()
             a.solve_raw(self.desc, self.problem, self.result)
             if integrate:
                 a.integrate_checked(self.dmodel, B, self.d_q, self.d_dq, self.d_status, self.d_fail, self.steps_done)
@@ -950,4 +1009,11 @@ class DeviceRollout:
         if getattr(self, "d_active", None) is not None:
             self.api.release(self.d_active)
             self.d_active = None
+        for name in ("d_com", "d_com_target"):
+            if getattr(self, name, None) is not None:
+                self.api.release(getattr(self, name))
+                setattr(self, name, None)
+        if getattr(self, "dcom", None) is not None:
+            self.api.com_destroy(self.dcom)
+            self.dcom = None
         self.api.model_destroy(self.dmodel)

@@ -1081,6 +1081,8 @@ def _solve_hybrid(configurations, tasks, dt, damping, limits, barriers, constrai
     frame_slots = hybrid.plan(model, slots, cslots)
     if frame_slots is None:
         return None
+    if hybrid.com_slot(slots) is not None and not hasattr(api, "com_task"):  # (a solver without the centre-of-mass kernel)
+        return None
     if limits is None:  # model defaults, pink/solve_ik.py:94-105
         model.ensure_limits()
         limits = [model.configuration_limit, model.velocity_limit]
@@ -1126,7 +1128,7 @@ def _record_stats(result, route: str) -> None:
 
 def last_solve_stats() -> dict:
     """What the last :func:`solve_ik_batch` call of this process did: ``route`` (``"device"``: kinematics, rows and QP
-    formed on the device from ``q``; ``"hybrid"``: FrameTask rows formed on the device from ``q``, the other tasks /
+    formed on the device from ``q``; ``"hybrid"``: FrameTask rows (and one ComTask's) formed on the device from ``q``, the other tasks /
     limits / barriers evaluated on the host, QP on the device; ``"host-evaluated"``: everything evaluated on the host,
     QP on the device), ``instances``, ``failed``, ``iters_mean`` and ``paths`` -- the share of the batch per solver path
     (:meth:`pink_amd.batch_solver.BatchResult.path_fractions`; ``handover`` is the share that paid for both solvers)."""
