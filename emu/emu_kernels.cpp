@@ -310,6 +310,21 @@ int pinkhip_emu_plan_solve(const pinkhip_desc *d, int out[6]) {
   if (!rc) plan_out(p, out);
   return rc;
 }
+// ... of a whole control step (warm: its warm-start twin, NULL: pinkhip_rollout_step_device), in the same form; nothing runs
+int pinkhip_emu_plan_rollout(const pinkhip_desc *d, void *mp, const pinkhip_rollout_step *st, const pinkhip_warm *warm, int out[6]) {
+  if (!d || !mp || !st) {
+    g_err = "null descriptor / model / args";
+    return PINKHIP_E_INVALID;
+  }
+  const EmuModel *m = static_cast<const EmuModel *>(mp);
+  pinkhip::HostTables t;
+  pinkhip::RolloutArgs ra{};
+  LaunchPlan p;
+  int rc = prepare(d, t, ra.k);
+  if (!rc) rc = pinkhip::plan_rollout(*d, m->dev, m->image.has_relative, *st, warm, std::getenv("PINKHIP_SOLVER"), ra, p, g_err);
+  if (!rc) plan_out(p, out);
+  return rc;
+}
 int pinkhip_emu_rollout_step_pairs(const pinkhip_desc *d, void *mp, const pinkhip_rollout_step *st, const pinkhip_sphere_pairs *sp) {
   LaunchPlan p;
   return rollout_step_pairs(d, mp, st, sp, true, p);

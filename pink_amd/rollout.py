@@ -544,6 +544,9 @@ class DeviceRollout:
         return tables
 
     def _launch_whole_step(self, st, lo: int = 0) -> bool:
+        # (the one place a filled RolloutStep leaves for the library, from _one_kernel_step and _one_kernel_step_range:
+        # tests/whole_step_cases.py and tests/test_whole_step_table.py replace it on an instance to read the struct or to
+        # alter the launch -- keep the name and the (st, lo) -> bool signature, or change them there too)
         if self._pairs is not None:
             return self.api.rollout_step_pairs(self.desc, self.dmodel, st, self._pairs)
         if self.warm_start:
