@@ -210,6 +210,25 @@ int pinkhip_emu_com_task(void *mp, void *cp, long long B, const double *q, const
   if (B == 0) return PINKHIP_OK;
   return run_fk(m->dev, B, lane_main_com<8>, lane_main_com<32>, lane_main_com<64>, &a);
 }
+// the ManipulabilityTask row, mirroring pinkhip_manipulability_task_device on host memory
+int pinkhip_emu_manipulability_task(void *mp, long long B, const double *q, int frame, int reference_frame, int row_mask, double rate,
+                                    double *e, long long sE, double *J, long long sJ, int row0, double *m_out) {
+  if (!mp) return pinkhip::refuse(g_err, PINKHIP_E_INVALID, "null handle / model");
+  const EmuModel *m = static_cast<const EmuModel *>(mp);
+  pinkhip::ManipArgs a{m->dev, B, q, frame, reference_frame, row_mask, __builtin_popcount(row_mask & 63), rate, e, J, sE, sJ, row0, m_out};
+  if (const char *bad = pinkhip::manip_task_fault(a)) return pinkhip::refuse(g_err, PINKHIP_E_INVALID, bad);
+  if (const char *bad = pinkhip::manip_path_fault(m->dev.nj, m->dev.parent, m->dev.jtype, m->dev.frame_joint[frame]))
+    return pinkhip::refuse(g_err, PINKHIP_E_UNSUPPORTED, bad);
+  if (B == 0) return PINKHIP_OK;
+  return run_fk(m->dev, B, lane_main_manip<8>, lane_main_manip<32>, lane_main_manip<64>, &a);
+}
+// Test infrastructure: the path check on a tree given as its tables, without a device model in front of it (a model of more
+// than 64 joints cannot be created: nv <= PINKHIP_MAX_NV)
+int pinkhip_emu_manipulability_path_check(int nj, const int *parent, const int *jtype, int frame_joint) {
+  g_err.clear();
+  if (const char *bad = pinkhip::manip_path_fault(nj, parent, jtype, frame_joint)) return pinkhip::refuse(g_err, PINKHIP_E_UNSUPPORTED, bad);
+  return PINKHIP_OK;
+}
 int pinkhip_emu_step(void *mp, long long B, const pinkhip_step *st) {
   EmuModel *m = static_cast<EmuModel *>(mp);
   pinkhip::FkArgs a = pinkhip::step_args(m->dev, B, *st);

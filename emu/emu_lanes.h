@@ -13,6 +13,7 @@
 #include "../pink_amd/csrc/ik_frame_task.h"
 #include "../pink_amd/csrc/ik_kinematics.h"
 #include "../pink_amd/csrc/ik_com.h"
+#include "../pink_amd/csrc/ik_manip.h"
 #include "../pink_amd/csrc/ik_rollout.h"
 #include "../pink_amd/csrc/model_tables.h"
 #include "../pink_amd/csrc/host_tables.h"
@@ -78,6 +79,11 @@ void lane_main_step(void *p) {
 template <int W>
 void lane_main_com(void *p) {
   pinkhip::ik_com_instance<W>(*static_cast<const pinkhip::ComArgs *>(p), pinkhip::block_id());
+}
+
+template <int W>
+void lane_main_manip(void *p) {
+  pinkhip::ik_manip_instance<W>(*static_cast<const pinkhip::ManipArgs *>(p), pinkhip::block_id());
 }
 
 }  // namespace pinkemu

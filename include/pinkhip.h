@@ -459,6 +459,29 @@ int pinkhip_com_task_device(pinkhip_handle *h, const pinkhip_model *model, const
                             const double *q, const double *target, int32_t target_batched, double *e, int64_t sE,
                             double *J, int64_t sJ, int32_t row0, double *com_out);
 
+/* ---- ManipulabilityTask row (pink/tasks/manipulability_task.py): the gradient of Yoshikawa's index, formed on the device ----
+ * With J the rows `row_mask` keeps (bit i = row i, twists [v; w]) of the 6 x nv Jacobian of frame slot `frame` of the
+ * model -- reference_frame PINKHIP_FRAME_LOCAL: the body Jacobian; PINKHIP_FRAME_WORLD: the spatial one, twists taken at
+ * the world origin -- A = J J^T (r x r) and m = sqrt(det A), the call writes for every instance b
+ *     e[b sE + row0]           = -rate
+ *     J[b sJ + row0 nv + j]    = d m / d (tangent coordinate j)        j = 0..nv-1
+ * and m_out [B] when it is not NULL; nothing else in e / J is written.  Columns of joints that are not ancestors of the
+ * frame are exactly zero.  Singular A: A = L D L^T without pivoting, and a pivot <= r eps max_i A_ii gives m = 0 and an
+ * exactly zero row (the reference's pinv(A) returns round-off there).  With sE = K and sJ = Kd nv the row lands in
+ * pinkhip_problem.e / .J behind the frame and centre-of-mass rows.  Only strides too small for the row (sE < row0 + 1,
+ * sJ < (row0 + 1) nv) are caught.  Enqueued on the handle's current compute stream, asynchronous.
+ *
+ * Refused, having touched nothing: PINKHIP_E_INVALID for a NULL pointer, a frame index outside the model, an empty
+ * mask (or bits above 5), a reference frame that is neither, row0 < 0, such strides; PINKHIP_E_UNSUPPORTED for a joint
+ * between the root and the frame that is not revolute (the reference refuses those too), or nj > 64 (one lane per joint). */
+#define PINKHIP_HAS_MANIPULABILITY_TASK 1
+#define PINKHIP_FRAME_LOCAL 0
+#define PINKHIP_FRAME_WORLD 1
+int pinkhip_manipulability_task_device(pinkhip_handle *h, const pinkhip_model *model, int64_t B, const double *q,
+                                       int32_t frame, int32_t reference_frame, int32_t row_mask /* bit i = row i kept */,
+                                       double rate, double *e, int64_t sE, double *J, int64_t sJ, int32_t row0,
+                                       double *m_out /* [B] or NULL */);
+
 /* q [B,nq], q_target [nq] or [B,nq] -> lb, ub [B,nv]; posture error written into e [B,K] at columns
  * e_off .. e_off + nv - root_nv (e may be NULL) */
 int pinkhip_limits_posture_device(pinkhip_handle *h, const pinkhip_model *model, int64_t B, double dt,

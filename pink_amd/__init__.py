@@ -9,14 +9,14 @@ __version__ = "0.1.0"
 
 from .batch import IKBatch, pack_terms
 from .batch_solver import BatchResult, BatchSolver
-from .configuration import Configuration, ConfigurationBatch, Model, build_chain, load_urdf
+from .configuration import Configuration, ConfigurationBatch, Model, ReferenceFrame, build_chain, load_urdf
 from .exceptions import NoSolutionFound, NotWithinConfigurationLimits, PinkError, TargetNotSet
 from .sharding import MultiDeviceSolver
 from .solve_ik import build_ik, clear_device_cache, last_solve_stats, pack_configurations, pinned_empty, solve_ik, solve_ik_batch
-from .tasks import ComTask, DampingTask, FrameTask, PostureTask, Task
+from .tasks import ComTask, DampingTask, FrameTask, ManipulabilityTask, PostureTask, Task
 
 __all__ = [
-    "BatchResult", "BatchSolver", "ComTask", "Configuration", "ConfigurationBatch", "DampingTask", "FrameTask", "IKBatch", "Model", "MultiDeviceSolver", "NoSolutionFound",
-    "NotWithinConfigurationLimits", "PinkError", "PostureTask", "TargetNotSet", "Task", "build_chain", "build_ik", "clear_device_cache",
+    "BatchResult", "BatchSolver", "ComTask", "Configuration", "ConfigurationBatch", "DampingTask", "FrameTask", "IKBatch", "ManipulabilityTask", "Model", "MultiDeviceSolver", "NoSolutionFound",
+    "NotWithinConfigurationLimits", "PinkError", "PostureTask", "ReferenceFrame", "TargetNotSet", "Task", "build_chain", "build_ik", "clear_device_cache",
     "last_solve_stats", "load_urdf", "pack_configurations", "pinned_empty", "pack_terms", "solve_ik", "solve_ik_batch",
 ]

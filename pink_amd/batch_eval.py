@@ -134,6 +134,31 @@ def _com_task(kin: BatchKinematics, col, solver=None):
     return DenseTaskTerm(J=kin.jacobian_center_of_mass(), e=e, cost=_costs(col, 3), gain=t0.gain, lm_damping=t0.lm_damping)
 
 
+def manipulability_slot_is_uniform(col: Sequence, with_weights: bool = False) -> bool:
+    """Frame, mask, reference frame and rate of a ManipulabilityTask slot are the same for every instance?  ``with_weights``:
+    gain, lm_damping and cost as well (what the hybrid route asks of a slot; :func:`_check_slot` refuses a differing gain /
+    lm_damping on the host route, a differing cost is served there)."""
+    t0 = col[0]
+    if _same(col):
+        return True
+    if any(t.frame != t0.frame or t.reference_frame != t0.reference_frame or t.row_mask != t0.row_mask
+           or t.manipulability_rate != t0.manipulability_rate for t in col):
+        return False
+    return not with_weights or all(t.gain == t0.gain and t.lm_damping == t0.lm_damping and t.cost == t0.cost for t in col)
+
+
+def _manipulability_task(kin: BatchKinematics, col, solver=None):
+    """``pink/tasks/manipulability_task.py:343-415``: ``e = [-rate]``, ``J = dm / dq`` (one row), the batch at once."""
+    from .tasks.manipulability_task import manipulability_rows
+
+    t0, B = col[0], kin.B
+    if not manipulability_slot_is_uniform(col):
+        raise PinkError("frame / mask / reference frame / rate of one ManipulabilityTask slot must be the same for every instance of a batch")
+    _, Jm = manipulability_rows(kin.frame_jacobian(t0.frame, t0.reference_frame), t0.mask)
+    e = np.full((B, 1), -float(t0.manipulability_rate))
+    return DenseTaskTerm(J=Jm[:, None, :], e=e, cost=_costs(col, 1), gain=t0.gain, lm_damping=t0.lm_damping)
+
+
 def _posture_task(kin: BatchKinematics, col, solver=None):
     """``pink/tasks/posture_task.py:100-107``: ``q (-) q*`` on the actuated coordinates."""
     t0, B = col[0], kin.B
@@ -225,10 +250,11 @@ def _task_evaluators():
     from .tasks.com_task import ComTask
     from .tasks.frame_task import FrameTask
     from .tasks.linear_holonomic_task import JointCouplingTask, JointVelocityTask, LinearHolonomicTask
+    from .tasks.manipulability_task import ManipulabilityTask
     from .tasks.posture_task import DampingTask, LowAccelerationTask, PostureTask
     from .tasks.relative_frame_task import RelativeFrameTask
 
-    return {ComTask: _com_task, FrameTask: _frame_task, RelativeFrameTask: _relative_frame_task, PostureTask: _posture_task,
+    return {ComTask: _com_task, ManipulabilityTask: _manipulability_task, FrameTask: _frame_task, RelativeFrameTask: _relative_frame_task, PostureTask: _posture_task,
             DampingTask: _damping_task, LowAccelerationTask: _low_acceleration_task, JointVelocityTask: _joint_velocity_task,
             LinearHolonomicTask: _linear_holonomic_task, JointCouplingTask: _linear_holonomic_task}
 

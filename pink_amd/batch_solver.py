@@ -118,6 +118,8 @@ class BatchSolver:
             raise PinkHipError(rc, (self._lib.pinkhip_last_error(None) or b"").decode())
         self._h = h
         self.device_id = device_id
+        if hasattr(self._lib, "pinkhip_manipulability_task_device"):  # (PINKHIP_HAS_MANIPULABILITY_TASK)
+            self.manipulability_task = self._manipulability_task
 
     @staticmethod
     def sharded(device_ids, solver_factory=None):
@@ -431,6 +433,17 @@ class BatchSolver:
         """The three ComTask rows of every instance into ``e`` / ``J`` at row ``row0`` (``pinkhip_com_task_device``)."""
         self._check(self._lib.pinkhip_com_task_device(self._h, ctypes.c_void_p(model), ctypes.c_void_p(com), B, q, target,
                                                       int(bool(target_batched)), e, sE, J, sJ, int(row0), com_out))
+
+    def _manipulability_task(self, model: int, B: int, q: int, frame: int, reference_frame: int, row_mask: int, rate: float,
+                            e: int, sE: int, J: int, sJ: int, row0: int, m_out=None) -> None:
+        """The ManipulabilityTask row of every instance into ``e`` / ``J`` at row ``row0``
+        (``pinkhip_manipulability_task_device``): ``frame`` is a frame slot of the device model, ``reference_frame`` 0
+        (LOCAL) or 1 (WORLD), bit ``i`` of ``row_mask`` keeps row ``i`` of the frame's Jacobian; ``m_out [B]`` receives the
+        manipulability itself.  The library refuses (``PinkHipError`` -5) a path that is not all revolute.  Bound to the
+        solver as ``manipulability_task`` only when the loaded library has the symbol: ``hasattr(solver,
+        "manipulability_task")`` is how the routes ask (a library without it serves the host route)."""
+        self._check(self._lib.pinkhip_manipulability_task_device(self._h, ctypes.c_void_p(model), B, q, int(frame), int(reference_frame),
+                                                                 int(row_mask), float(rate), e, sE, J, sJ, int(row0), m_out))
 
     def step_kernel(self, model: int, B: int, args) -> None:
         """Whole control step around the solve in one launch (``pinkhip_step_device``)."""

@@ -15,6 +15,7 @@ Jacobian is the *body* Jacobian (``pin.LOCAL``); a free-flyer has
 
 from __future__ import annotations
 
+import enum
 import logging
 import xml.etree.ElementTree as ET
 from dataclasses import dataclass
@@ -62,6 +63,14 @@ def _adjoint(T: SE3) -> np.ndarray:
     A[:3, 3:] = px @ R
     A[3:, 3:] = R
     return A
+
+
+class ReferenceFrame(enum.IntEnum):
+    """Frame a Jacobian's twists are expressed in (the two of ``pin.ReferenceFrame`` the reference's tasks use; the
+    values are this project's -- ``include/pinkhip.h``: ``PINKHIP_FRAME_LOCAL`` / ``_WORLD``)."""
+
+    LOCAL = 0
+    WORLD = 1
 
 
 @dataclass
@@ -312,16 +321,20 @@ class Configuration:
                 raise NotWithinConfigurationLimits(i, q[i], lo[i], up[i])
             logging.warning("Value %f at index %d is out of limits: [%f, %f]", q[i], i, lo[i], up[i])
 
-    def get_frame_jacobian(self, frame: str) -> np.ndarray:
-        """Body Jacobian of ``frame`` (6 x nv, ``configuration.py:203-236``)."""
+    def get_frame_jacobian(self, frame: str, reference_frame: int = 0) -> np.ndarray:
+        """Body Jacobian of ``frame`` (6 x nv, ``configuration.py:203-236``); with ``reference_frame=ReferenceFrame.WORLD``
+        the spatial Jacobian, twists ``[v; w]`` taken at the world origin (``pin.getFrameJacobian(..., pin.WORLD)``)."""
         m = self.model
+        if reference_frame not in (ReferenceFrame.LOCAL, ReferenceFrame.WORLD):
+            raise ValueError(f"invalid reference frame {reference_frame}; only LOCAL and WORLD are supported")
+        world = reference_frame == ReferenceFrame.WORLD
         f = m.frames[m.getFrameId(frame)]
         J = np.zeros((6, m.nv))
         oMf_inv = self.oMf[m.getFrameId(frame)].inverse()
         j = f.joint
         while j >= 0:
             jt = m.joints[j]
-            A = _adjoint(oMf_inv * self.oMi[j])  # joint frame -> frame
+            A = _adjoint(self.oMi[j] if world else oMf_inv * self.oMi[j])  # joint frame -> world / frame
             if jt.kind == "revolute":
                 J[:, jt.idx_v] = A[:, 3:] @ jt.axis
             elif jt.kind == "prismatic":

@@ -21,6 +21,7 @@
 #include "ik_frame_task.h"
 #include "ik_kinematics.h"
 #include "ik_com.h"
+#include "ik_manip.h"
 #include "ik_rollout.h"
 #include "host_tables.h"
 #include "model_tables.h"
@@ -729,6 +730,37 @@ int pinkhip_com_task_device(pinkhip_handle *h, const pinkhip_model *m, const pin
     hipLaunchKernelGGL(pinkhip::ik_com_task_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
   } else {
     hipLaunchKernelGGL(pinkhip::ik_com_task_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
+  }
+  PH_HIP(h, hipGetLastError());
+  return PINKHIP_OK;
+}
+
+int pinkhip_manipulability_task_device(pinkhip_handle *h, const pinkhip_model *m, int64_t B, const double *q, int32_t frame,
+                                       int32_t reference_frame, int32_t row_mask, double rate, double *e, int64_t sE,
+                                       double *J, int64_t sJ, int32_t row0, double *m_out) {
+  if (!h || !m) return fail(h, PINKHIP_E_INVALID, "null handle / model");
+  const pinkhip::ManipArgs a{m->dev, B, q, frame, reference_frame, row_mask, __builtin_popcount(row_mask & 63), rate, e, J, sE, sJ,
+                             row0, m_out};
+  if (const char *bad = pinkhip::manip_task_fault(a)) return fail(h, PINKHIP_E_INVALID, bad);
+  {
+    const char *base = m->image.bytes.data();
+    const int *parent = reinterpret_cast<const int *>(base + m->image.off_parent);
+    const int *jtype = reinterpret_cast<const int *>(base + m->image.off_jtype);
+    const int *frame_joint = reinterpret_cast<const int *>(base + m->image.off_frame_joint);
+    if (const char *bad = pinkhip::manip_path_fault(m->image.nj, parent, jtype, frame_joint[frame]))
+      return fail(h, PINKHIP_E_UNSUPPORTED, bad);
+  }
+  if (B == 0) return PINKHIP_OK;
+  PH_HIP(h, hipSetDevice(h->device));
+  const int per = pinkhip::com_lds_doubles(m->dev.nj);
+  const dim3 block(pinkhip::kWave);
+  const int width = m->dev.nv > m->dev.nj ? m->dev.nv : m->dev.nj;  // (the group width of the other row kernels of this model)
+  if (width <= 8) {
+    hipLaunchKernelGGL(pinkhip::ik_manipulability_task_kernel<8>, dim3((unsigned)((B + 7) / 8)), block, 8 * 8 * per + 16, h->stream, a);
+  } else if (width <= 32) {
+    hipLaunchKernelGGL(pinkhip::ik_manipulability_task_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
+  } else {
+    hipLaunchKernelGGL(pinkhip::ik_manipulability_task_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
   }
   PH_HIP(h, hipGetLastError());
   return PINKHIP_OK;

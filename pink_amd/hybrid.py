@@ -26,16 +26,19 @@ from .batch_solver import split_iters
 from .exceptions import PinkError
 
 MAX_FRAME_TASKS = 16
+MAX_MANIPULABILITY_TASKS = 4
 
 
 def plan(kin_model, slots: Sequence, constraints) -> Optional[List[int]]:
     """Indices of the FrameTask slots when the hybrid route serves this stack, else ``None``: at least one FrameTask,
-    at most one ComTask on a model that carries mass (two or more: the host evaluates them), every other task of a
+    at most one ComTask on a model that carries mass (two or more: the host evaluates them), at most four
+    ManipulabilityTask slots (each with one frame, mask, reference frame and rate for the whole batch), every other task of a
     class whose batched evaluator yields a diagonal term; equality constraints (slots of ``constraints=``) made of
     FrameTasks / RelativeFrameTasks."""
     from .tasks.com_task import ComTask
     from .tasks.frame_task import FrameTask
     from .tasks.linear_holonomic_task import JointVelocityTask
+    from .tasks.manipulability_task import ManipulabilityTask
     from .tasks.posture_task import DampingTask, LowAccelerationTask, PostureTask
     from .tasks.relative_frame_task import RelativeFrameTask
 
@@ -63,8 +66,14 @@ def plan(kin_model, slots: Sequence, constraints) -> Optional[List[int]]:
     coms = [k for k, col in enumerate(slots) if type(col[0]) is ComTask]
     if len(coms) > 1 or (coms and not (kin_model.total_mass > 0.0 and len(kin_model.joints) <= 64)):
         return None
+    manips = manipulability_slots(slots)
+    if len(manips) > MAX_MANIPULABILITY_TASKS or (manips and len(kin_model.joints) > 64):
+        return None
+    for k in manips:  # (a per-instance list that differs in frame / mask / reference frame / rate / gain / cost: the host route, as frame slots)
+        if any(type(t) is not ManipulabilityTask for t in slots[k]) or not be.manipulability_slot_is_uniform(slots[k], with_weights=True):
+            return None
     for k, col in enumerate(slots):
-        if k not in frames and k not in coms and type(col[0]) not in (PostureTask, DampingTask, LowAccelerationTask, JointVelocityTask):
+        if k not in frames and k not in coms and k not in manips and type(col[0]) not in (PostureTask, DampingTask, LowAccelerationTask, JointVelocityTask):
             return None
     return frames
 
@@ -74,6 +83,13 @@ def com_slot(slots: Sequence) -> Optional[int]:
     from .tasks.com_task import ComTask
 
     return next((k for k, col in enumerate(slots) if type(col[0]) is ComTask), None)
+
+
+def manipulability_slots(slots: Sequence) -> List[int]:
+    """Indices of the ManipulabilityTask slots of a stack, in stack order."""
+    from .tasks.manipulability_task import ManipulabilityTask
+
+    return [k for k, col in enumerate(slots) if type(col[0]) is ManipulabilityTask]
 
 
 class HybridState:
@@ -89,6 +105,7 @@ class HybridState:
         self.bufs = {}
         self.cframes, self.carrays, self.cmodel = None, None, None  # device model of the equality constraints' frames
         self.dcom, self.com_key = None, None  # device copy of the model's mass tables (a ComTask slot)
+        self.mframes, self.marrays, self.mmodel = None, None, None  # device model of the ManipulabilityTask slots' frames
 
     def com_tables(self) -> int:
         """The device mass tables of the model as it is NOW (an edit of a mass or a centre builds them anew)."""
@@ -101,6 +118,20 @@ class HybridState:
             self.dcom = self.api.com_create(self.dmodel, mass, com)
             self.com_key = key
         return self.dcom
+
+    def manipulability_model(self, frames) -> int:
+        """Device model whose frame slots are the frames of the ManipulabilityTask slots (the frame-task model's slots each
+        own six rows of the frame kernel)."""
+        frames = tuple(frames)
+        if self.mframes != frames:
+            from .rollout import ModelArrays
+
+            if self.mmodel is not None:
+                self.api.model_destroy(self.mmodel)
+            self.marrays = ModelArrays(self.model, list(frames))
+            self.mmodel = self.api.model_create(self.marrays.desc)
+            self.mframes = frames
+        return self.mmodel
 
     def constraint_model(self, frames) -> int:
         frames = tuple(frames)
@@ -133,6 +164,9 @@ class HybridState:
         if self.dcom is not None:
             self.api.com_destroy(self.dcom)
             self.dcom = None
+        if self.mmodel is not None:
+            self.api.model_destroy(self.mmodel)
+            self.mmodel = None
         self.api.model_destroy(self.dmodel)
 
 
@@ -148,7 +182,10 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     kc = com_slot(slots)
     ccol = None if kc is None else slots[kc]
     nc = 0 if ccol is None else 1
-    diag = [be.task_term(kq, col, None) for k, col in enumerate(slots) if k not in frame_slots and k != kc]
+    km = manipulability_slots(slots)
+    mcols = [slots[k] for k in km]
+    nm = len(mcols)
+    diag = [be.task_term(kq, col, None) for k, col in enumerate(slots) if k not in frame_slots and k != kc and k not in km]
     if any(not isinstance(t, DiagonalTaskTerm) for t in diag):
         raise PinkError("hybrid route: a task outside the FrameTasks produced a dense Jacobian")
     lb = np.full((B, nv), -np.inf)
@@ -174,13 +211,19 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     if ccol is not None:
         be._check_slot(ccol)
         ctarget = np.ascontiguousarray(be.com_targets(ccol, B), dtype=np.float64)
-    Kd = 6 * nf + 3 * nc
+    # ... and one dense task of one row per ManipulabilityTask slot behind those
+    for col in mcols:
+        be._check_slot(col)
+    Kd = 6 * nf + 3 * nc + nm
     K = Kd + b0.K
     fcost = [be._costs(col, 6) for col in fcols]
-    widths = [6] * nf + [3] * nc
+    widths = [6] * nf + [3] * nc + [1] * nm
     if ccol is not None:
         fcost.append(be._costs(ccol, 3))
         fcols = fcols + [ccol]
+    for col in mcols:
+        fcost.append(be._costs(col, 1))
+        fcols = fcols + [col]
     batched = b0.cost.ndim == 2 or any(np.ndim(c) == 2 for c in fcost)
     if batched:
         cost = np.concatenate([np.broadcast_to(np.asarray(c, dtype=float), (B, w)) for c, w in zip(fcost, widths)]
@@ -194,14 +237,15 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     targets = np.ascontiguousarray(np.stack([_targets_of(col, B) for col in fcols[:nf]], axis=1))  # [B, nf, 12]
     i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)  # noqa: E731
     f64 = lambda v: np.ascontiguousarray(v, dtype=np.float64)  # noqa: E731
-    task_rows = i32([6 * i for i in range(nf + 1)] + [Kd] * nc + [Kd + int(r) for r in b0.task_rows[1:]])
-    task_kind = i32([0] * (nf + nc) + list(b0.task_kind))
-    task_col0 = i32([0] * (nf + nc) + list(b0.task_col0))
+    task_rows = i32([6 * i for i in range(nf + 1)] + [6 * nf + 3] * nc + [6 * nf + 3 * nc + i + 1 for i in range(nm)]
+                    + [Kd + int(r) for r in b0.task_rows[1:]])
+    task_kind = i32([0] * (nf + nc + nm) + list(b0.task_kind))
+    task_col0 = i32([0] * (nf + nc + nm) + list(b0.task_col0))
     gain = f64([col[0].gain for col in fcols] + list(b0.gain))
     lm = f64([col[0].lm_damping for col in fcols] + list(b0.lm_damping))
     brow, bsafe = i32(b0.barrier_rows), f64(b0.barrier_safe_gain if b0.barrier_safe_gain.size else [0.0])
     d = Desc()
-    d.B, d.nv, d.T, d.Kd, d.K, d.md, d.n_eq = B, nv, nf + nc + len(diag), Kd, K, b0.md, n_eq
+    d.B, d.nv, d.T, d.Kd, d.K, d.md, d.n_eq = B, nv, nf + nc + nm + len(diag), Kd, K, b0.md, n_eq
     d.task_rows, d.task_kind, d.task_col0 = (a.ctypes.data_as(c_int32_p) for a in (task_rows, task_kind, task_col0))
     d.gain, d.lm_damping = gain.ctypes.data_as(c_double_p), lm.ctypes.data_as(c_double_p)
     d.n_barriers = int(b0.barrier_safe_gain.size)
@@ -234,6 +278,12 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
         d_ct = s.buf("com_target", ctarget.nbytes)
         api.put(d_ct, ctarget)
         api.com_task(s.dmodel, s.com_tables(), B, d_q, d_ct, ctarget.ndim == 2, d_e, K, d_J, Kd * nv, 6 * nf)
+    if nm:  # one row per ManipulabilityTask slot behind the centre-of-mass rows, one launch each
+        mmodel = s.manipulability_model(col[0].frame for col in mcols)
+        for i, col in enumerate(mcols):
+            t0 = col[0]
+            api.manipulability_task(mmodel, B, d_q, i, int(t0.reference_frame), t0.row_mask, float(t0.manipulability_rate), d_e, K,
+                                    d_J, Kd * nv, 6 * nf + 3 * nc + i)
     if n_eq:
         # the same kernel on the constraints' frames, writing J into the leading rows of Gd and e into those of hd (row
         # pitches md nv and md); hd then becomes -gain e on the host: [B, md] doubles go home and back

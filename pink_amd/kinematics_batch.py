@@ -145,13 +145,28 @@ class BatchKinematics:
         return J
 
     # -- pink/configuration.py:203-236 ------------------------------------------------------------------
-    def frame_jacobian(self, frame: str) -> np.ndarray:
-        """Body Jacobian of ``frame``, ``[B, 6, nv]`` (``get_frame_jacobian``)."""
+    def frame_jacobian(self, frame: str, reference_frame: int = 0) -> np.ndarray:
+        """Body Jacobian of ``frame``, ``[B, 6, nv]`` (``get_frame_jacobian``); ``reference_frame=ReferenceFrame.WORLD``:
+        :meth:`frame_jacobian_world`."""
+        if reference_frame == 1:
+            return self.frame_jacobian_world(frame)
+        if reference_frame != 0:
+            raise ValueError(f"invalid reference frame {reference_frame}; only LOCAL and WORLD are supported")
         J = self._jacs.get(frame)
         if J is None:
             f = self.model.frames[self.model.getFrameId(frame)]
             Rf, pf = self.frame_pose(frame)
             J = self._jacs[frame] = self._jacobian_at(Rf, pf, f.joint, rotate=True)
+        return J
+
+    def frame_jacobian_world(self, frame: str) -> np.ndarray:
+        """Spatial Jacobian of ``frame``, ``[B, 6, nv]``: twists ``[v; w]`` taken at the world origin, in the world's axes
+        (``get_frame_jacobian(frame, ReferenceFrame.WORLD)``) -- the Jacobian of the world origin carried by the frame's joint."""
+        key = frame + "\0world"
+        J = self._jacs.get(key)
+        if J is None:
+            f = self.model.frames[self.model.getFrameId(frame)]
+            J = self._jacs[key] = self._jacobian_at(np.broadcast_to(np.eye(3), (self.B, 3, 3)), np.zeros((self.B, 3)), f.joint, rotate=False)
         return J
 
     def world_linear_jacobian(self, frame: str) -> np.ndarray:

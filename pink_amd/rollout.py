@@ -192,8 +192,14 @@ class DeviceRollout:
                  position_barriers: Sequence = (), floating_base_limit=None, const_tasks: Sequence = (),
                  diag_tasks: Sequence = (), acceleration_limit: Optional[np.ndarray] = None,
                  velocity_limit: Optional[np.ndarray] = None, constraint_slots: Sequence = (), warm_start: bool = False,
-                 com_task=None):
-        """``com_task``: a :class:`pink_amd.tasks.ComTask` (``pink/tasks/com_task.py``) whose three rows
+                 com_task=None, manipulability_tasks: Sequence = ()):
+        """``manipulability_tasks``: up to four :class:`pink_amd.tasks.ManipulabilityTask` (``pink/tasks/manipulability_task.py``)
+        whose one row each ``pinkhip_manipulability_task_device`` forms behind the FrameTask and ComTask rows, from the
+        configuration the step solves at (``fused=True``: step kernel, one launch per task, solve; ``fused=False``: the same
+        launches in front of the solve).  The whole-step kernel does not form these rows: ``fused="kernel"`` raises.
+        :meth:`manipulability` returns the indices themselves.
+
+        ``com_task``: a :class:`pink_amd.tasks.ComTask` (``pink/tasks/com_task.py``) whose three rows
         ``pinkhip_com_task_device`` forms behind the FrameTask rows, from the configuration the step solves at and the
         model's mass tables (``fused=True``: step kernel, centre-of-mass kernel, solve; ``fused=False``: one more launch in
         front of the solve).  The whole-step kernel does not form centre-of-mass rows: ``fused="kernel"`` raises.  The target
@@ -244,6 +250,20 @@ class DeviceRollout:
                 raise ValueError("the model carries no mass: its centre of mass is undefined")
             if len(model.joints) > 64:
                 raise ValueError("centre-of-mass rows on the device need a model of at most 64 joints")
+        self.manip_tasks, self.mmodel, self.d_manip = list(manipulability_tasks), None, None
+        if self.manip_tasks:
+            from .tasks.manipulability_task import ManipulabilityTask, check_revolute_path
+
+            if self.fused == "kernel":
+                raise ValueError('the whole-step kernel does not form manipulability rows: a ManipulabilityTask needs fused=True or fused=False')
+            if not hasattr(api, "manipulability_task"):
+                raise ValueError("this solver has no pinkhip_manipulability_task_device: a ManipulabilityTask needs it")
+            if len(self.manip_tasks) > 4 or any(type(t) is not ManipulabilityTask for t in self.manip_tasks):
+                raise ValueError("manipulability_tasks: at most four ManipulabilityTask objects")
+            if len(model.joints) > 64:
+                raise ValueError("manipulability rows on the device need a model of at most 64 joints")
+            for t in self.manip_tasks:
+                check_revolute_path(model, t.frame)
         # (a frame task (frame, ...) regulates the frame in the world; ((frame, root), ...) the pose of frame in root --
         # a RelativeFrameTask, pink/tasks/relative_frame_task.py: a relative slot of the device model)
         self.arrays = ModelArrays(model, [ft[0] for ft in frame_tasks], velocity_limit=velocity_limit)
@@ -271,7 +291,8 @@ class DeviceRollout:
         if self.n_crow and any(not np.array_equal(q_0, const_tasks[0][2]) for _, _, q_0, *_ in const_tasks):
             raise ValueError("constant-row tasks must share one reference configuration q_0")
         self.n_com = 3 if com_task is not None else 0
-        self.Kd = 6 * nf + self.n_crow + self.n_com  # (n_crow = 0 beside a ComTask: constant-row tasks need fused="kernel")
+        self.n_manip = len(self.manip_tasks)
+        self.Kd = 6 * nf + self.n_crow + self.n_com + self.n_manip  # (n_crow = 0 beside these: constant-row tasks need fused="kernel")
         n_post = nv - root_nv if posture_cost is not None else 0
         self.K = self.Kd + n_post + sum(e.shape[0] for _, e, *_ in diag_tasks)
         # task tables of the QP (include/pinkhip.h: frame tasks, constant-row tasks, then the diagonal ones: the posture first)
@@ -286,6 +307,9 @@ class DeviceRollout:
         if com_task is not None:  # three dense rows behind the frame rows
             rows.append(rows[-1] + 3), kind.append(0), col0.append(0), gain.append(float(com_task.gain)), lm.append(float(com_task.lm_damping))
             cost += list(np.broadcast_to(np.asarray(com_task.cost, float), (3,)))
+        for t in self.manip_tasks:  # one dense row each behind the centre-of-mass rows
+            rows.append(rows[-1] + 1), kind.append(0), col0.append(0), gain.append(float(t.gain)), lm.append(float(t.lm_damping))
+            cost.append(float(1.0 if t.cost is None else t.cost))
         if n_post:
             rows.append(rows[-1] + n_post), kind.append(1), col0.append(root_nv), gain.append(posture_gain), lm.append(posture_lm_damping)
             cost += [float(posture_cost)] * n_post
@@ -427,6 +451,10 @@ class DeviceRollout:
             self.dcom = a.com_create(self.dmodel, *model.mass_tables())
             self.d_com, self.d_com_target = f8(B, 3), f8(B, 3)
             self.set_com_target(be.com_targets([com_task], B))
+        if self.manip_tasks:  # (a device model of its own: every frame slot of dmodel owns six rows of the step kernel)
+            self.marrays = ModelArrays(model, [t.frame for t in self.manip_tasks])  # (kept: the descriptor points into its arrays)
+            self.mmodel = a.model_create(self.marrays.desc)
+            self.d_manip = f8(B, self.n_manip)
         if self.warm_start:  # one byte per robot and tangent coordinate, read and written in place by every step
             self.d_active = a.alloc(B * nv)
             a.put(self.d_active, np.zeros(B * nv, dtype=np.uint8))
@@ -649,6 +677,25 @@ class DeviceRollout:
         self.api.com_task(self.dmodel, self.dcom, self.B, self.d_q, self.d_com_target, self.com_batched, self.d_e, self.K,
                           self.d_J, self.Kd * self.nv, 6 * len(self.frames), self.d_com)
 
+    def _manip_rows(self, m_out: bool = False) -> None:
+        """The ManipulabilityTask rows of the configurations in ``d_q``, behind the frame and centre-of-mass rows."""
+        row0 = 6 * len(self.frames) + self.n_com
+        for i, t in enumerate(self.manip_tasks):
+            self.api.manipulability_task(self.mmodel, self.B, self.d_q, i, int(t.reference_frame), t.row_mask, float(t.manipulability_rate),
+                                         self.d_e, self.K, self.d_J, self.Kd * self.nv, row0 + i,
+                                         self.d_manip + 8 * self.B * i if m_out else None)
+
+    def manipulability(self) -> np.ndarray:
+        """``[n_tasks, B]``: manipulability indices of the current configurations, computed on the device."""
+        if not self.manip_tasks:
+            raise ValueError("this rollout has no ManipulabilityTask")
+        self.flush()
+        self._manip_rows(m_out=True)  # (the rows it writes are formed anew by every step)
+        self.api.sync()
+        m = np.zeros((self.n_manip, self.B))
+        self.api.get(m, self.d_manip)
+        return m
+
     def center_of_mass(self) -> np.ndarray:
         """``[B, 3]``: centres of mass of the current configurations, computed on the device."""
         if self.com_task is None:
@@ -698,6 +745,8 @@ class DeviceRollout:
             a.step_kernel(self.dmodel, B, st)
             if self.com_task is not None:  # (the step kernel has advanced q already)
                 self._com_rows()
+            if self.manip_tasks:
+                self._manip_rows()
             a.solve_raw(self.desc, self.problem, self.result)
             self._pending = bool(integrate)
         else:  # one launch for FK, one per FrameTask, limits + posture, solve, integrate
@@ -710,6 +759,8 @@ class DeviceRollout:
                              self.d_e if self.n_post else None, self.K, self.Kd)
             if self.com_task is not None:
                 self._com_rows()
+            if self.manip_tasks:
+                self._manip_rows()
             a.solve_raw(self.desc, self.problem, self.result)
             if integrate:
                 a.integrate_checked(self.dmodel, B, self.d_q, self.d_dq, self.d_status, self.d_fail, self.steps_done)
@@ -1012,7 +1063,10 @@ class DeviceRollout:
         if getattr(self, "d_active", None) is not None:
             self.api.release(self.d_active)
             self.d_active = None
-        for name in ("d_com", "d_com_target"):
+        if getattr(self, "mmodel", None) is not None:
+            self.api.model_destroy(self.mmodel)
+            self.mmodel = None
+        for name in ("d_com", "d_com_target", "d_manip"):
             if getattr(self, name, None) is not None:
                 self.api.release(getattr(self, name))
                 setattr(self, name, None)

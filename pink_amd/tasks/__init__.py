@@ -1,10 +1,11 @@
 """Kinematic tasks (``pink/tasks``)."""
 from .com_task import ComTask
 from .frame_task import FrameTask
+from .manipulability_task import ManipulabilityTask
 from .linear_holonomic_task import JointCouplingTask, JointVelocityTask, LinearHolonomicTask
 from .posture_task import DampingTask, LowAccelerationTask, PostureTask
 from .relative_frame_task import RelativeFrameTask
 from .task import Task
 
-__all__ = ["Task", "ComTask", "FrameTask", "RelativeFrameTask", "PostureTask", "DampingTask", "LowAccelerationTask",
+__all__ = ["Task", "ComTask", "FrameTask", "RelativeFrameTask", "ManipulabilityTask", "PostureTask", "DampingTask", "LowAccelerationTask",
            "LinearHolonomicTask", "JointCouplingTask", "JointVelocityTask"]
