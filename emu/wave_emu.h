@@ -114,6 +114,7 @@ inline void pin8(const double (&)[4], const double (&)[4]) {}
 template <typename T>
 inline void pin(T &) {}
 inline void opaque(double &) {}
+inline void forget(double &) {}  // (the device code declares the value dead; here it simply stays)
 inline int opaque_uniform(int x) { return x; }
 template <class Args>
 inline const Args *kernarg_reload(const Args &a) {

@@ -29,10 +29,12 @@ struct HbmTerms {
 // from lane k.  M holds at least NV entries (the first NV are used); ci and mu_l accumulate this lane's entry of c
 // and its share of the Levenberg-Marquardt term.
 // DEPTH: a chunk of eight rows is accumulated in ~1 k cycles of this wave's own issue time, a request takes several
-// thousand under load -- with ONE chunk ahead (DEPTH = 1) a wave of the sweep-tableau kernel waited out the memory
-// latency once per chunk (section clock, round 4: 30 k cycles per wave in this phase, whatever the input regime);
-// DEPTH = 2 has all 24 rows of the headline stack in flight before the first FMA.  (an on-the-fly source delivers
-// one FrameTask = six rows per chunk and nothing is in flight)
+// thousand under load -- with ONE chunk ahead (DEPTH = 1) a lone wave waits out the memory latency once per chunk
+// (section clock, round 4: 30 k cycles per wave in this phase, whatever the input regime); DEPTH = 2 has all 24 rows of
+// the headline stack in flight before the first FMA.  The stack + solve kernels at three waves per SIMD are built with
+// DEPTH = 1 (ik_sweep.h: PINKHIP_STACK_DEPTH -- the other waves of the SIMD issue during the wait, and the third chunk
+// buffer is 20 registers the kernel does not have), those at two waves per SIMD with DEPTH = 2
+// (PINKHIP_STACK_DEPTH_WIDE).  (an on-the-fly source delivers one FrameTask = six rows per chunk and nothing is in flight)
 // `mid` runs between the first requests and the first accumulation: what else the caller wants from HBM (bounds,
 // the terms of the diagonal tasks) is requested there and arrives within the same wait.
 struct NoMid {
@@ -64,12 +66,46 @@ struct WaveSplit {
 #ifndef PINKHIP_WAVE_SPLIT
 #define PINKHIP_WAVE_SPLIT(Src) (!Src::kOnTheFly)
 #endif
+// Two switches of the stacking that remove work and change no bit of any result, on where the streams are addressed through
+// a WaveSplit (DIAG below: the stack + solve kernels with rows from HBM); off, the device code is what it was.
+//   ROLE_BUFFERS     the chunk loop is unrolled by the number of chunk buffers, so that a buffer changes its ROLE from trip to
+//                    trip -- requested into, accumulated from -- instead of being copied into its neighbour at the end of
+//                    every chunk (Kd is a run-time value, the loop is rolled: `buf[d] = buf[d + 1]` was 12 v_mov_b64 per
+//                    chunk of eight rows at DEPTH = 1).  The same requests, the same rows in the same order.
+//   SKIP_ZERO_ROWS   a task row whose weight is exactly zero is not multiplied (a FrameTask with orientation cost 0, as in
+//                    examples/humanoid_draco3.py; the slots of frames that only a barrier needs).  One ballot
+//                    per chunk over `wa == 0 && gw == 0` in the lane that holds the row's weights; row kk is a CANDIDATE if
+//                    that holds in lane kk of EVERY group of the wave (per-instance costs: in both instances); a candidate
+//                    is skipped if one more ballot finds every lane's entry of the row finite, and with NX > 0 the row's front
+//                    entries (lane kk's px) finite as well.  Every other row takes the ordinary path.  Why no bit changes:
+//                      * what the row would add to an accumulator is (+-0 * finite) or (finite * +-0): +-0 -- aa itself
+//                        is fma(+-0, r, +0) = +0 for a finite r, the products into M[j], *hdiag and front->m are +-0 * finite,
+//                        the one into ci is (gw = +-0) * finite;
+//                      * every one of those accumulators starts at +0.0 and only ever receives sums under
+//                        round-to-nearest, which give -0.0 only for (-0) + (-0) -- and, the one exception, for an FMA
+//                        whose exact result is negative and below half the smallest denormal (|product| < 2^-1075 into an
+//                        accumulator that is still zero): that rounds to -0.0.  Short of that underflow none of them is
+//                        ever -0.0;
+//                      * so acc + (+-0) == acc bit for bit, zero or not.  (In the underflow case the multiplied row
+//                        would turn the -0.0 into +0.0 and the skipped one leaves it: a zero of the other sign, with
+//                        entries of J below 1e-160.)
+//                    A NaN gw (a non-finite error or gain: 0 * inf, 0 * NaN) fails the first compare, an inf or NaN in the
+//                    row the second: the NaN such a row makes of H is made as before.  The per-lane terms outside the row
+//                    loop (mu_l, the front's hxx / cx) are computed as before.  The row is still requested: the finite test
+//                    needs it, and the kernel is not short of HBM bandwidth.
+#ifndef PINKHIP_STACK_ROLE_BUFFERS
+#define PINKHIP_STACK_ROLE_BUFFERS(Src) PINKHIP_WAVE_SPLIT(Src)
+#endif
+#ifndef PINKHIP_STACK_SKIP_ZERO_ROWS
+#define PINKHIP_STACK_SKIP_ZERO_ROWS(Src) PINKHIP_WAVE_SPLIT(Src)
+#endif
 // DIAG: *hdiag follows this lane's own diagonal entry M[li] (lane li, li < NV) in a register of its own -- the product the
 // broadcast-FMA of column li forms in lane li is this lane's own row entry times its own factor: the same FMA on the
 // same operands, bit for bit what M[li] receives -- so that the caller does not have to pick "register li of lane li"
 // out of the row afterwards (NV compares and 2 NV selects).  It also takes the instance as `ws` (b = ws.first + ws.rel)
 // and addresses the streams as described at WaveSplit: the same addresses.  Off: nothing changes.
-template <int NV, int W, int RCMAX, class Src, int DEPTH = 1, int NX = 0, bool DIAG = false, int NM, class Mid = NoMid>
+// ROLE_OK: the caller's veto of ROLE_BUFFERS for an instantiation in which the unrolled loop costs registers.
+template <int NV, int W, int RCMAX, class Src, int DEPTH = 1, int NX = 0, bool DIAG = false, bool ROLE_OK = true, int NM, class Mid = NoMid>
 __device__ __forceinline__ void stack_rows_bcast(const KernelArgs &a, long long b, Src *terms, bool in, int li,
                                                  double (&M)[NM], double &ci, double &mu_l, Mid mid = Mid(), StackFront<NX> *front = nullptr,
                                                  double *hdiag = nullptr, WaveSplit ws = WaveSplit()) {
@@ -79,6 +115,8 @@ __device__ __forceinline__ void stack_rows_bcast(const KernelArgs &a, long long 
   const int nv = a.nv, Kd = a.Kd, K = a.K;
   // (SPLIT: the scalar bases of the wave and this lane's offsets from them; a.cost is per instance or one for all)
   constexpr bool SPLIT = DIAG && PINKHIP_WAVE_SPLIT(Src);
+  constexpr bool ROLES = SPLIT && ROLE_OK && PINKHIP_STACK_ROLE_BUFFERS(Src);
+  constexpr bool ZSKIP = SPLIT && PINKHIP_STACK_SKIP_ZERO_ROWS(Src);
   const double *Jb = a.J + (SPLIT ? ws.first : b) * (long long)Kd * nv;
   const double *eb = a.e + (SPLIT ? ws.first : b) * (long long)K;
   const double *costb = a.cost_batched ? a.cost + (SPLIT ? ws.first : b) * (long long)K : a.cost;
@@ -133,53 +171,156 @@ __device__ __forceinline__ void stack_rows_bcast(const KernelArgs &a, long long 
       }
     }
   };
+  auto forget_chunk = [&](Chunk &dst) {
+#pragma unroll
+    for (int kk = 0; kk < RC; ++kk) forget(dst.r[kk]);
+    forget(dst.pw), forget(dst.pe), forget(dst.pg), forget(dst.pl);
+#pragma unroll
+    for (int x = 0; x < NX; ++x) forget(dst.px[x]);
+  };
   if (Kd > 0) {
 #pragma unroll
     for (int d = 0; d < NB - 1; ++d)
       if (d * RC < Kd) request(buf[d], d * RC);  // wave-uniform
   }
   mid();
-  for (int r0 = 0; r0 < Kd; r0 += RC) {
-    const int rc = (Kd - r0 < RC) ? Kd - r0 : RC;
-    if (r0 + (NB - 1) * RC < Kd) request(buf[NB - 1], r0 + (NB - 1) * RC);
-    const Chunk &cur = buf[0];
-    const double wa = (li < rc) ? cur.pw * cur.pw : 0.0;
-    const double gw = (li < rc) ? cur.pg * wa * cur.pe : 0.0;
-    if (li < rc) mu_l += cur.pl * (cur.pg * cur.pg) * wa * cur.pe * cur.pe;
-    const BcT wab = bcast_prepare<W>(wa), gwb = bcast_prepare<W>(gw);
-    BcT pxb[NX > 0 ? NX : 1];
-    if constexpr (NX > 0) {
-      // (lane kk's own row: its part of the uniform entries)
-      front->hxx[0] = fma(wa * cur.px[0], cur.px[0], front->hxx[0]);
-      front->cx[0] = fma(gw, cur.px[0], front->cx[0]);
-      if constexpr (NX == 2) {
-        front->hxx[1] = fma(wa * cur.px[0], cur.px[1], front->hxx[1]);
-        front->hxx[2] = fma(wa * cur.px[1], cur.px[1], front->hxx[2]);
-        front->cx[1] = fma(gw, cur.px[1], front->cx[1]);
+  if constexpr (!ROLES && !ZSKIP) {
+    // (the switches off: this loop as it always was -- the device code of its users does not change by a byte)
+    for (int r0 = 0; r0 < Kd; r0 += RC) {
+      const int rc = (Kd - r0 < RC) ? Kd - r0 : RC;
+      if (r0 + (NB - 1) * RC < Kd) request(buf[NB - 1], r0 + (NB - 1) * RC);
+      const Chunk &cur = buf[0];
+      const double wa = (li < rc) ? cur.pw * cur.pw : 0.0;
+      const double gw = (li < rc) ? cur.pg * wa * cur.pe : 0.0;
+      if (li < rc) mu_l += cur.pl * (cur.pg * cur.pg) * wa * cur.pe * cur.pe;
+      const BcT wab = bcast_prepare<W>(wa), gwb = bcast_prepare<W>(gw);
+      BcT pxb[NX > 0 ? NX : 1];
+      if constexpr (NX > 0) {
+        // (lane kk's own row: its part of the uniform entries)
+        front->hxx[0] = fma(wa * cur.px[0], cur.px[0], front->hxx[0]);
+        front->cx[0] = fma(gw, cur.px[0], front->cx[0]);
+        if constexpr (NX == 2) {
+          front->hxx[1] = fma(wa * cur.px[0], cur.px[1], front->hxx[1]);
+          front->hxx[2] = fma(wa * cur.px[1], cur.px[1], front->hxx[2]);
+          front->cx[1] = fma(gw, cur.px[1], front->cx[1]);
+        }
+#pragma unroll
+        for (int x = 0; x < NX; ++x) pxb[x] = bcast_prepare<W>(cur.px[x]);
       }
+      static_for<0, RC>([&](auto Kc) {
+        constexpr int kk = decltype(Kc)::value;
+        if (kk < rc) {  // wave-uniform
+          // (the row's own uses first: the row copies of the broadcast are then made in its registers)
+          const double aa = fma_bcast<W, kk>(0.0, wab, cur.r[kk]);
+          ci = fma_bcast<W, kk>(ci, gwb, cur.r[kk]);
+          if constexpr (DIAG) *hdiag = fma(cur.r[kk], aa, *hdiag);
+          const BcT rowb = bcast_prepare<W>(cur.r[kk]);
+          static_for<0, NV>([&](auto Jc) {
+            constexpr int j = decltype(Jc)::value;
+            M[j] = fma_bcast<W, j>(M[j], rowb, aa);
+          });
+          if constexpr (NX > 0) {
 #pragma unroll
-      for (int x = 0; x < NX; ++x) pxb[x] = bcast_prepare<W>(cur.px[x]);
+            for (int x = 0; x < NX; ++x) front->m[x] = fma_bcast<W, kk>(front->m[x], pxb[x], aa);  // H[li][x] += (w^2 J[k][li]) J[k][x]
+          }
+        }
+      });
+#pragma unroll
+      for (int d = 0; d + 1 < NB; ++d) buf[d] = buf[d + 1];
     }
-    static_for<0, RC>([&](auto Kc) {
-      constexpr int kk = decltype(Kc)::value;
-      if (kk < rc) {  // wave-uniform
-        // (the row's own uses first: the row copies of the broadcast are then made in its registers)
-        const double aa = fma_bcast<W, kk>(0.0, wab, cur.r[kk]);
-        ci = fma_bcast<W, kk>(ci, gwb, cur.r[kk]);
-        if constexpr (DIAG) *hdiag = fma(cur.r[kk], aa, *hdiag);
-        const BcT rowb = bcast_prepare<W>(cur.r[kk]);
-        static_for<0, NV>([&](auto Jc) {
-          constexpr int j = decltype(Jc)::value;
-          M[j] = fma_bcast<W, j>(M[j], rowb, aa);
-        });
-        if constexpr (NX > 0) {
+  } else {
+    // chunk [r0, r0 + RC) out of `cur`
+    auto accumulate = [&](const Chunk &cur, int r0) {
+      const int rc = (Kd - r0 < RC) ? Kd - r0 : RC;
+      const double wa = (li < rc) ? cur.pw * cur.pw : 0.0;
+      const double gw = (li < rc) ? cur.pg * wa * cur.pe : 0.0;
+      if (li < rc) mu_l += cur.pl * (cur.pg * cur.pg) * wa * cur.pe * cur.pe;
+      // bit kk: row kk of the chunk is multiplied (wave-uniform, scalar)
+      unsigned live = rc >= RC ? (1u << RC) - 1u : (1u << rc) - 1u;
+      if constexpr (ZSKIP) {
+        // (lanes li >= rc have wa = gw = 0: their bits are set, and `live` has none for them)
+        unsigned long long cand = wave_ballot(wa == 0.0 && gw == 0.0);
 #pragma unroll
-          for (int x = 0; x < NX; ++x) front->m[x] = fma_bcast<W, kk>(front->m[x], pxb[x], aa);  // H[li][x] += (w^2 J[k][li]) J[k][x]
+        for (int g = 1; g < kWave / W; ++g) cand &= cand >> (W & 63);  // (bit kk < W: lane kk of every group)
+        unsigned c = static_cast<unsigned>(cand) & live;
+        // wave-uniform: no chunk of a stack without zero weights comes here (the test is on a copy the compiler cannot see
+        // through: it would replace this one branch by the RC tests of the single bits)
+        if (opaque_uniform(static_cast<int>(c)) != 0) {
+          if constexpr (NX > 0) {
+            bool pf = fabs(cur.px[0]) < INFINITY;  // (false for an inf and for a NaN)
+            if constexpr (NX == 2) pf = pf && fabs(cur.px[1]) < INFINITY;
+            unsigned long long pm = wave_ballot(pf);
+#pragma unroll
+            for (int g = 1; g < kWave / W; ++g) pm &= pm >> (W & 63);
+            c &= static_cast<unsigned>(pm);
+          }
+          static_for<0, RC>([&](auto Kc) {
+            constexpr int kk = decltype(Kc)::value;
+            if ((c >> kk) & 1u) {
+              if (wave_ballot(!(fabs(cur.r[kk]) < INFINITY)) == 0ull) live &= ~(1u << kk);
+            }
+          });
         }
       }
-    });
+      const BcT wab = bcast_prepare<W>(wa), gwb = bcast_prepare<W>(gw);
+      BcT pxb[NX > 0 ? NX : 1];
+      if constexpr (NX > 0) {
+        // (lane kk's own row: its part of the uniform entries)
+        front->hxx[0] = fma(wa * cur.px[0], cur.px[0], front->hxx[0]);
+        front->cx[0] = fma(gw, cur.px[0], front->cx[0]);
+        if constexpr (NX == 2) {
+          front->hxx[1] = fma(wa * cur.px[0], cur.px[1], front->hxx[1]);
+          front->hxx[2] = fma(wa * cur.px[1], cur.px[1], front->hxx[2]);
+          front->cx[1] = fma(gw, cur.px[1], front->cx[1]);
+        }
 #pragma unroll
-    for (int d = 0; d + 1 < NB; ++d) buf[d] = buf[d + 1];
+        for (int x = 0; x < NX; ++x) pxb[x] = bcast_prepare<W>(cur.px[x]);
+      }
+      static_for<0, RC>([&](auto Kc) {
+        constexpr int kk = decltype(Kc)::value;
+        if (ZSKIP ? __builtin_expect(((live >> kk) & 1u) != 0u, 1) : kk < rc) {  // wave-uniform
+          // (the row's own uses first: the row copies of the broadcast are then made in its registers)
+          const double aa = fma_bcast<W, kk>(0.0, wab, cur.r[kk]);
+          ci = fma_bcast<W, kk>(ci, gwb, cur.r[kk]);
+          if constexpr (DIAG) *hdiag = fma(cur.r[kk], aa, *hdiag);
+          const BcT rowb = bcast_prepare<W>(cur.r[kk]);
+          static_for<0, NV>([&](auto Jc) {
+            constexpr int j = decltype(Jc)::value;
+            M[j] = fma_bcast<W, j>(M[j], rowb, aa);
+          });
+          if constexpr (NX > 0) {
+#pragma unroll
+            for (int x = 0; x < NX; ++x) front->m[x] = fma_bcast<W, kk>(front->m[x], pxb[x], aa);  // H[li][x] += (w^2 J[k][li]) J[k][x]
+          }
+        }
+      });
+    };
+    if constexpr (ROLES) {
+      // NB chunks per trip: chunk s of a trip is accumulated out of buf[s] while buf[s - 1] -- free since the chunk before --
+      // takes the request NB - 1 chunks ahead
+      for (int r0 = 0; r0 < Kd; r0 += NB * RC) {
+        static_for<0, NB>([&](auto Sc) {
+          constexpr int s = decltype(Sc)::value;
+          const int r = r0 + s * RC;
+          if (r < Kd) {  // wave-uniform
+            // (no request: the buffer's registers are dead, and said to be -- carried round the loop as they were, a row's
+            // permlane swaps would have to spare them: two more v_mov_b32 per row)
+            if (r + (NB - 1) * RC < Kd) request(buf[(s + NB - 1) % NB], r + (NB - 1) * RC);
+            else forget_chunk(buf[(s + NB - 1) % NB]);
+            accumulate(buf[s], r);
+          } else {
+            forget_chunk(buf[(s + NB - 1) % NB]);
+          }
+        });
+      }
+    } else {
+      for (int r0 = 0; r0 < Kd; r0 += RC) {
+        if (r0 + (NB - 1) * RC < Kd) request(buf[NB - 1], r0 + (NB - 1) * RC);
+        accumulate(buf[0], r0);
+#pragma unroll
+        for (int d = 0; d + 1 < NB; ++d) buf[d] = buf[d + 1];
+      }
+    }
   }
 }
 

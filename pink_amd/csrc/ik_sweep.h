@@ -70,6 +70,11 @@ static __device__ unsigned long long pinkhip_clock[16];  // one copy per transla
 #ifndef PINKHIP_STACK_DEPTH_WIDE  // (instantiations at two waves per SIMD: 256 registers)
 #define PINKHIP_STACK_DEPTH_WIDE 2
 #endif
+// the chunk loop of the stacking unrolled by its buffers (ik_stack_rows.h: ROLE_BUFFERS) -- not in <30, 8, 64>: two more
+// spilled SGPRs there, 16 -> 18
+#ifndef PINKHIP_SWEEP_STACK_ROLE_BUFFERS
+#define PINKHIP_SWEEP_STACK_ROLE_BUFFERS(NV, MD, W) (!((NV) == 30 && (MD) == 8 && (W) == 64))
+#endif
 // Column p of the tableau (group-uniform run-time p) read with the VGPR index mode from register tuples (TabRegs,
 // ik_common.h) instead of NT broadcast-FMAs against the indicator of p: groups of 32 and 64 lanes (one or two reads per
 // wave; four groups of 16 lanes would pay as much as the FMAs they replace)
@@ -297,9 +302,9 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   if constexpr (NE > 0) {
     KernelArgs af = a;  // (the rows as the lanes see them: NE columns in)
     af.J = a.J + NE;
-    stack_rows_bcast<NV, W, 8, Src, PINKHIP_STACK_DEPTH, NE, DREG>(af, b, terms, in, li, T, ci, mu_l, others, &front, &hii, ws);
+    stack_rows_bcast<NV, W, 8, Src, PINKHIP_STACK_DEPTH, NE, DREG, PINKHIP_SWEEP_STACK_ROLE_BUFFERS(NVT, MD, W)>(af, b, terms, in, li, T, ci, mu_l, others, &front, &hii, ws);
   } else {
-    stack_rows_bcast<NV, W, 8, Src, (NT > 34 ? PINKHIP_STACK_DEPTH_WIDE : PINKHIP_STACK_DEPTH), 0, DREG>(a, b, terms, in, li, T, ci, mu_l, others, nullptr, &hii, ws);
+    stack_rows_bcast<NV, W, 8, Src, (NT > 34 ? PINKHIP_STACK_DEPTH_WIDE : PINKHIP_STACK_DEPTH), 0, DREG, PINKHIP_SWEEP_STACK_ROLE_BUFFERS(NVT, MD, W)>(a, b, terms, in, li, T, ci, mu_l, others, nullptr, &hii, ws);
   }
   ci += ci_d;
   mu_l += mu_d;

@@ -155,6 +155,17 @@ __device__ __forceinline__ void pin(T &x) {
 // into a select.  Emits no instruction.
 __device__ __forceinline__ void opaque(double &x) { asm volatile("" : "+v"(x)); }
 
+// A value that is dead from here on, said to the compiler: an empty asm "writes" x, so the old value does not have to be kept --
+// for a register that is carried round a loop on a path that never reads it again.  Emits no instruction; x is undefined
+// afterwards.
+__device__ __forceinline__ void forget(double &x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "=v"(x));
+#else  // the host pass of hipcc only parses device functions
+  (void)x;
+#endif
+}
+
 // ... and a wave-uniform int (kept in a scalar register)
 __device__ __forceinline__ int opaque_uniform(int x) {
   asm volatile("" : "+s"(x));

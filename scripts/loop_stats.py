@@ -9,7 +9,7 @@ VGPR-index reads): what DESIGN.md's per-trip and per-region tables are counted f
 The tableau loop is found from the control-flow graph, not from the compiler's "in Loop" comments (it writes those for
 natural loops only, and they pointed at the stacking loop of the hand-over code once the tableau loop was none): it is the
 strongly connected component of basic blocks that holds the column read with the VGPR index mode (s_set_gpr_idx_on).
-Three reports:
+Four reports:
 
   * the loop, block by block, with each block's successors and the part it is counted in;
   * the ORDINARY TRIP: the blocks of the loop an exchange executes, with its scalar instructions and, among them, its
@@ -21,7 +21,13 @@ Three reports:
   * the INITIAL SWEEPS: the blocks in front of the loop that hold a row's worth of broadcast-FMAs behind one
     bcast_prepare, with the plain 64-bit register moves of each (a row rotated through its registers shows as ~NT / 3 or
     more v_mov_b64), and the vector instructions of the blocks between them: the always-executed tests in front of
-    each sweep.
+    each sweep;
+  * the START-UP (the stacking, ik_stack_rows.h): a STACKED ROW is a block in front of the initial sweeps that holds a row's
+    worth of broadcast-FMAs and no reciprocal.  Reported: the vector instructions of all blocks between kernel entry and the
+    first stacked row, and among them the 64-bit address computations (v_lshl_add_u64, v_mad_u64_u32) and the memory requests;
+    the vector instructions per stacked row; and the chunk loop -- the strongly connected component that holds the stacked rows --
+    outside its rows: its vector and scalar instructions, its 64-bit address computations and its register-to-register
+    v_mov_b64 (a chunk buffer copied into its neighbour; `v_mov_b64 v[..], 0` is a default, not a copy).
 """
 import re
 import sys
@@ -42,7 +48,7 @@ def parse(path):
         m = LABEL.match(l)
         if m or cur is None:
             name = (m.group(1) if m.group(1) else 'bb.' + m.group(2)) if m else 'entry'
-            cur = dict(name=name, line=i + 1, valu=0, dppf=0, salu=0, cbr=0, nop=0, ds=0, scr=0, idx=0, mov64=0, swap=0, ops={}, succ=[], term=False)
+            cur = dict(name=name, line=i + 1, valu=0, dppf=0, salu=0, cbr=0, nop=0, ds=0, scr=0, idx=0, mov64=0, cp64=0, a64=0, vmem=0, swap=0, ops={}, succ=[], term=False)
             blocks.append(cur)
             if m:
                 continue
@@ -56,6 +62,10 @@ def parse(path):
                 cur['dppf'] += 1
             if op.startswith('v_mov_b64') and 'dpp' not in op:
                 cur['mov64'] += 1
+                if re.match(r'v_mov_b64\S*\s+v\[\d+:\d+\],\s*v\[', s):
+                    cur['cp64'] += 1
+            if op.startswith(('v_lshl_add_u64', 'v_mad_u64_u32', 'v_mad_i64_i32')):
+                cur['a64'] += 1
             if op.startswith('v_permlane'):
                 cur['swap'] += 1
         elif op == 's_nop':
@@ -63,6 +73,8 @@ def parse(path):
         elif op.startswith('ds_'):
             if not op.startswith(('ds_bpermute', 'ds_permute', 'ds_swizzle')):  # (the crossbar: no LDS memory)
                 cur['ds'] += 1
+        elif op.startswith(('global_load', 'buffer_load', 'flat_load')):
+            cur['vmem'] += 1
         elif op.startswith('scratch_'):
             cur['scr'] += 1
         elif op == 's_set_gpr_idx_on':
@@ -192,6 +204,26 @@ def main():
         while n > 0 and blocks[n]['valu'] == 0:
             n -= 1
         show(blocks[n], blocks, 'in front')
+        startup(blocks, front[0])
+
+
+def startup(blocks, first_sweep):
+    rows = [n for n in range(first_sweep) if blocks[n]['dppf'] >= 12 and blocks[n]['swap'] and not blocks[n]['ops'].get('v_rcp_f64_e32')]
+    if not rows:
+        return
+    print("\n-- start-up (stacking)")
+    head = blocks[:rows[0]]
+    print(f"ENTRY TO FIRST STACKED ROW: {sum(b['valu'] for b in head)} VALU, of which {sum(b['a64'] for b in head)} 64-bit address computations; "
+          f"{sum(b['salu'] for b in head)} SALU, of which {sum(b['cbr'] for b in head)} conditional branches; {sum(b['vmem'] for b in head)} memory requests, "
+          f"in {len(head)} blocks (all paths)")
+    vs = [blocks[n]['valu'] for n in rows]
+    print(f"STACKED ROWS: {len(rows)} blocks, VALU min {min(vs)} max {max(vs)}, broadcast-FMAs {blocks[rows[0]]['dppf']}, SALU min "
+          f"{min(blocks[n]['salu'] for n in rows)} max {max(blocks[n]['salu'] for n in rows)}")
+    comp = component_of(blocks, rows[0])
+    rest = [blocks[n] for n in comp if n not in rows]
+    print(f"CHUNK LOOP: {len(comp)} blocks of which {sum(1 for n in comp if n in rows)} stacked rows; outside the rows: {sum(b['valu'] for b in rest)} VALU, "
+          f"of which {sum(b['cp64'] for b in rest)} register-to-register v_mov_b64 and {sum(b['a64'] for b in rest)} 64-bit address computations; "
+          f"{sum(b['salu'] for b in rest)} SALU, of which {sum(b['cbr'] for b in rest)} conditional branches; {sum(b['vmem'] for b in rest)} memory requests")
 
 
 if __name__ == '__main__':
