@@ -229,6 +229,35 @@ int pinkhip_emu_manipulability_path_check(int nj, const int *parent, const int *
   if (const char *bad = pinkhip::manip_path_fault(nj, parent, jtype, frame_joint)) return pinkhip::refuse(g_err, PINKHIP_E_UNSUPPORTED, bad);
   return PINKHIP_OK;
 }
+// the RollingTask / OmniwheelTask rows, mirroring pinkhip_rolling_tasks_device on host memory
+int pinkhip_emu_rolling_tasks(void *mp, long long B, const double *q, int n, const int *slot, const int *kind, const double *radius,
+                              double *e, long long sE, double *J, long long sJ, int row0, double *height_out) {
+  if (!mp) return pinkhip::refuse(g_err, PINKHIP_E_INVALID, "null handle / model");
+  const EmuModel *m = static_cast<const EmuModel *>(mp);
+  pinkhip::RollingArgs a{m->dev, B, q, 0, {}, {}, {}, e, J, sE, sJ, row0, height_out};
+  if (const char *bad = pinkhip::rolling_set_wheels(a, n, slot, kind, radius)) return pinkhip::refuse(g_err, PINKHIP_E_INVALID, bad);
+  int code = PINKHIP_E_INVALID;
+  if (const char *bad = pinkhip::rolling_task_fault(a, m->dev.frame_root_joint, code)) return pinkhip::refuse(g_err, code, bad);
+  if (B == 0) return PINKHIP_OK;
+  const int width = pinkhip::rolling_group_width(m->dev.nj), per = pinkhip::kWave / width;
+  const pinkhip::LaneFn fn = width == 8 ? lane_main_rolling<8> : width == 32 ? lane_main_rolling<32> : lane_main_rolling<64>;
+  for (long long b = 0; b < (B + per - 1) / per; ++b) pinkhip::emu_run_block(b, fn, &a);
+  return PINKHIP_OK;
+}
+// Test infrastructure: the joint-count refusal on a bare count, without a device model in front of it (a model of more than
+// 64 joints cannot be created: nv <= PINKHIP_MAX_NV)
+int pinkhip_emu_rolling_joint_check(int nj) {
+  g_err.clear();
+  pinkhip::RollingArgs a{};
+  a.m.nj = nj;
+  a.m.nf = 1;
+  a.n = 1;
+  a.radius[0] = 0.1;
+  const int root_joint[1] = {-1};
+  int code = PINKHIP_OK;
+  if (const char *bad = pinkhip::rolling_task_fault(a, root_joint, code)) return pinkhip::refuse(g_err, code, bad);
+  return PINKHIP_OK;
+}
 int pinkhip_emu_step(void *mp, long long B, const pinkhip_step *st) {
   EmuModel *m = static_cast<EmuModel *>(mp);
   pinkhip::FkArgs a = pinkhip::step_args(m->dev, B, *st);

@@ -14,6 +14,7 @@
 #include "../pink_amd/csrc/ik_kinematics.h"
 #include "../pink_amd/csrc/ik_com.h"
 #include "../pink_amd/csrc/ik_manip.h"
+#include "../pink_amd/csrc/ik_rolling.h"
 #include "../pink_amd/csrc/ik_rollout.h"
 #include "../pink_amd/csrc/model_tables.h"
 #include "../pink_amd/csrc/host_tables.h"
@@ -84,6 +85,11 @@ void lane_main_com(void *p) {
 template <int W>
 void lane_main_manip(void *p) {
   pinkhip::ik_manip_instance<W>(*static_cast<const pinkhip::ManipArgs *>(p), pinkhip::block_id());
+}
+
+template <int W>
+void lane_main_rolling(void *p) {
+  pinkhip::ik_rolling_instance<W>(*static_cast<const pinkhip::RollingArgs *>(p), pinkhip::block_id());
 }
 
 }  // namespace pinkemu

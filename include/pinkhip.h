@@ -482,6 +482,32 @@ int pinkhip_manipulability_task_device(pinkhip_handle *h, const pinkhip_model *m
                                        double rate, double *e, int64_t sE, double *J, int64_t sJ, int32_t row0,
                                        double *m_out /* [B] or NULL */);
 
+/* ---- RollingTask / OmniwheelTask rows (pink/tasks/rolling_task.py, omniwheel_task.py): wheel contacts, formed on the device ----
+ * Wheel w of the n <= PINKHIP_MAX_WHEELS wheels of a call is the RELATIVE frame slot slot[w] of the model (frame = hub H,
+ * root = floor F: pinkhip_model_desc.frame_root_joint / frame_root_placement), of kind[w] and radius[w] = rho.  With (R_H, p_H)
+ * and (R_F, p_F) the world poses, z = (R_F^T (p_H - p_F))_z and p_C = p_H - rho R_F e_z the contact point, the call writes
+ * for every instance b, into the rows r = row0 + sum_{v<w} (3 or 2) of e [b sE + .] and J [b sJ + . nv + j]:
+ *     PINKHIP_WHEEL_ROLLING   e = (0, 0, z - rho);  J = the velocity of p_C, carried by the hub's body, in the floor's axes,
+ *                             per unit tangent velocity (three rows)
+ *     PINKHIP_WHEEL_OMNI      rows 0 and 2 of those three
+ * and z into height_out [b n + w] when it is not NULL; nothing else in e / J is written, and these rows are written
+ * completely: columns of joints that are not ancestors of the hub are exactly zero (the floor is taken as inertial, as the
+ * reference takes it: a floor on a moving joint moves R_F and p_F, but its ancestors own no column).  slot, kind and radius
+ * are HOST arrays, copied before the call returns.  One launch serves all wheels: the world poses of the joints are
+ * composed once.  Enqueued on the handle's current compute stream, asynchronous.
+ *
+ * Refused, having touched nothing: PINKHIP_E_INVALID for a NULL pointer, n outside 1..8, a slot outside the model or
+ * without a root, a kind that is neither, a radius that is not finite, row0 < 0, strides smaller than the rows
+ * (sE < row0 + rows, sJ < (row0 + rows) nv); PINKHIP_E_UNSUPPORTED for nj > 64 (one lane per joint).  B = 0 is fine. */
+#define PINKHIP_HAS_ROLLING_TASK 1
+#define PINKHIP_MAX_WHEELS 8
+#define PINKHIP_WHEEL_ROLLING 0   /* 3 rows */
+#define PINKHIP_WHEEL_OMNI    1   /* 2 rows: rows 0 and 2 of the three */
+int pinkhip_rolling_tasks_device(pinkhip_handle *h, const pinkhip_model *model, int64_t B, const double *q,
+                                 int32_t n, const int32_t *slot /* [n] host */, const int32_t *kind /* [n] host */,
+                                 const double *radius /* [n] host */, double *e, int64_t sE, double *J, int64_t sJ,
+                                 int32_t row0, double *height_out /* [B, n] device or NULL: z per wheel */);
+
 /* q [B,nq], q_target [nq] or [B,nq] -> lb, ub [B,nv]; posture error written into e [B,K] at columns
  * e_off .. e_off + nv - root_nv (e may be NULL) */
 int pinkhip_limits_posture_device(pinkhip_handle *h, const pinkhip_model *model, int64_t B, double dt,

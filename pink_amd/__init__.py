@@ -13,10 +13,10 @@ from .configuration import Configuration, ConfigurationBatch, Model, ReferenceFr
 from .exceptions import NoSolutionFound, NotWithinConfigurationLimits, PinkError, TargetNotSet
 from .sharding import MultiDeviceSolver
 from .solve_ik import build_ik, clear_device_cache, last_solve_stats, pack_configurations, pinned_empty, solve_ik, solve_ik_batch
-from .tasks import ComTask, DampingTask, FrameTask, ManipulabilityTask, PostureTask, Task
+from .tasks import ComTask, DampingTask, FrameTask, ManipulabilityTask, OmniwheelTask, PostureTask, RollingTask, Task
 
 __all__ = [
     "BatchResult", "BatchSolver", "ComTask", "Configuration", "ConfigurationBatch", "DampingTask", "FrameTask", "IKBatch", "ManipulabilityTask", "Model", "MultiDeviceSolver", "NoSolutionFound",
-    "NotWithinConfigurationLimits", "PinkError", "PostureTask", "ReferenceFrame", "TargetNotSet", "Task", "build_chain", "build_ik", "clear_device_cache",
+    "NotWithinConfigurationLimits", "OmniwheelTask", "PinkError", "PostureTask", "ReferenceFrame", "RollingTask", "TargetNotSet", "Task", "build_chain", "build_ik", "clear_device_cache",
     "last_solve_stats", "load_urdf", "pack_configurations", "pinned_empty", "pack_terms", "solve_ik", "solve_ik_batch",
 ]

@@ -145,7 +145,7 @@ ABI_SYMBOLS = (
     "pinkhip_limits_posture_device", "pinkhip_check_limits_device", "pinkhip_integrate_device", "pinkhip_integrate_checked_device",
     "pinkhip_pose_targets_device", "pinkhip_solve_warm_device", "pinkhip_rollout_step_warm_device",
     "pinkhip_rollout_step_pairs_device", "pinkhip_com_create", "pinkhip_com_destroy", "pinkhip_com_task_device",
-    "pinkhip_manipulability_task_device",
+    "pinkhip_manipulability_task_device", "pinkhip_rolling_tasks_device",
     "pinkhip_comm_get_unique_id", "pinkhip_comm_init", "pinkhip_comm_gather", "pinkhip_comm_gather_bytes",
     "pinkhip_comm_allgather_bytes", "pinkhip_comm_destroy",
     "pinkhip_host_alloc", "pinkhip_host_free", "pinkhip_malloc", "pinkhip_free",
@@ -199,6 +199,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.pinkhip_com_task_device.argtypes = [vp, vp, vp, i64, vp, vp, i32, vp, i64, vp, i64, i32, vp]
     if hasattr(lib, "pinkhip_manipulability_task_device"):  # (PINKHIP_HAS_MANIPULABILITY_TASK: a library without it serves the host route)
         lib.pinkhip_manipulability_task_device.argtypes = [vp, vp, i64, vp, i32, i32, i32, f64, vp, i64, vp, i64, i32, vp]
+    if hasattr(lib, "pinkhip_rolling_tasks_device"):  # (PINKHIP_HAS_ROLLING_TASK: a library without it serves the host route)
+        lib.pinkhip_rolling_tasks_device.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, vp, i64, vp, i64, i32, vp]
     lib.pinkhip_limits_posture_device.argtypes = [vp, vp, i64, f64, f64, vp, vp, i32, vp, vp, vp, i32, i32]
     lib.pinkhip_check_limits_device.argtypes = [vp, vp, i64, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_int64)]
     lib.pinkhip_integrate_device.argtypes = [vp, vp, i64, vp, vp]

@@ -159,6 +159,44 @@ def _manipulability_task(kin: BatchKinematics, col, solver=None):
     return DenseTaskTerm(J=Jm[:, None, :], e=e, cost=_costs(col, 1), gain=t0.gain, lm_damping=t0.lm_damping)
 
 
+def rolling_slot_is_uniform(col: Sequence, with_weights: bool = False) -> bool:
+    """Class, hub frame, floor frame and radius of a RollingTask / OmniwheelTask slot are the same for every instance?
+    ``with_weights``: gain, lm_damping and cost as well (what the hybrid route asks of a slot; :func:`_check_slot` refuses a
+    differing gain / lm_damping on the host route, a differing cost is served there)."""
+    t0 = col[0]
+    if _same(col):
+        return True
+    if any(type(t) is not type(t0) or t.hub_frame != t0.hub_frame or t.floor_frame != t0.floor_frame
+           or t.wheel_radius != t0.wheel_radius for t in col):
+        return False
+    return not with_weights or all(t.gain == t0.gain and t.lm_damping == t0.lm_damping
+                                   and np.array_equal(np.asarray(t.cost, dtype=float), np.asarray(t0.cost, dtype=float)) for t in col)
+
+
+def _rolling_task(kin: BatchKinematics, col, solver=None):
+    """``pink/tasks/rolling_task.py:79-139`` / ``omniwheel_task.py:33-72``: ``e = (0, 0, z - rho)``, ``J`` = the velocity of
+    the contact point in the floor's axes; the Omniwheel keeps rows 0 and 2.  A slot whose instances differ in frames or
+    radius is evaluated group by group."""
+    t0, B = col[0], kin.B
+    if not _same(col) and any(type(t) is not type(t0) for t in col):
+        raise PinkError("the class of one RollingTask / OmniwheelTask slot must be the same for every instance of a batch")
+    rows = list(t0.rows)
+    if rolling_slot_is_uniform(col):
+        z, J = kin.rolling_rows(t0.hub_frame, t0.floor_frame, float(t0.wheel_radius))
+        rho = float(t0.wheel_radius)
+    else:
+        z, J, rho = np.empty(B), np.empty((B, 3, kin.model.nv)), np.array([float(t.wheel_radius) for t in col])
+        keys = {}
+        for b, t in enumerate(col):
+            keys.setdefault((t.hub_frame, t.floor_frame, float(t.wheel_radius)), []).append(b)
+        for (hub, floor, r), idx in keys.items():
+            zk, Jk = kin.rolling_rows(hub, floor, r)
+            z[idx], J[idx] = zk[idx], Jk[idx]
+    e = np.zeros((B, 3))
+    e[:, 2] = z - rho
+    return DenseTaskTerm(J=np.ascontiguousarray(J[:, rows]), e=e[:, rows], cost=_costs(col, len(rows)), gain=t0.gain, lm_damping=t0.lm_damping)
+
+
 def _posture_task(kin: BatchKinematics, col, solver=None):
     """``pink/tasks/posture_task.py:100-107``: ``q (-) q*`` on the actuated coordinates."""
     t0, B = col[0], kin.B
@@ -253,8 +291,9 @@ def _task_evaluators():
     from .tasks.manipulability_task import ManipulabilityTask
     from .tasks.posture_task import DampingTask, LowAccelerationTask, PostureTask
     from .tasks.relative_frame_task import RelativeFrameTask
+    from .tasks.rolling_task import OmniwheelTask, RollingTask
 
-    return {ComTask: _com_task, ManipulabilityTask: _manipulability_task, FrameTask: _frame_task, RelativeFrameTask: _relative_frame_task, PostureTask: _posture_task,
+    return {RollingTask: _rolling_task, OmniwheelTask: _rolling_task, ComTask: _com_task, ManipulabilityTask: _manipulability_task, FrameTask: _frame_task, RelativeFrameTask: _relative_frame_task, PostureTask: _posture_task,
             DampingTask: _damping_task, LowAccelerationTask: _low_acceleration_task, JointVelocityTask: _joint_velocity_task,
             LinearHolonomicTask: _linear_holonomic_task, JointCouplingTask: _linear_holonomic_task}
 

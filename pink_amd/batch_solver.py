@@ -120,6 +120,8 @@ class BatchSolver:
         self.device_id = device_id
         if hasattr(self._lib, "pinkhip_manipulability_task_device"):  # (PINKHIP_HAS_MANIPULABILITY_TASK)
             self.manipulability_task = self._manipulability_task
+        if hasattr(self._lib, "pinkhip_rolling_tasks_device"):  # (PINKHIP_HAS_ROLLING_TASK)
+            self.rolling_tasks = self._rolling_tasks
 
     @staticmethod
     def sharded(device_ids, solver_factory=None):
@@ -444,6 +446,21 @@ class BatchSolver:
         "manipulability_task")`` is how the routes ask (a library without it serves the host route)."""
         self._check(self._lib.pinkhip_manipulability_task_device(self._h, ctypes.c_void_p(model), B, q, int(frame), int(reference_frame),
                                                                  int(row_mask), float(rate), e, sE, J, sJ, int(row0), m_out))
+
+    def _rolling_tasks(self, model: int, B: int, q: int, slots, kinds, radii, e: int, sE: int, J: int, sJ: int, row0: int,
+                       height_out=None) -> None:
+        """The RollingTask / OmniwheelTask rows of every instance into ``e`` / ``J`` from row ``row0`` on
+        (``pinkhip_rolling_tasks_device``), all wheels in one launch: ``slots[w]`` is a relative frame slot of the device
+        model (frame = hub, root = floor), ``kinds[w]`` 0 (rolling: three rows) or 1 (omniwheel: rows 0 and 2),
+        ``radii[w]`` the wheel radius; ``height_out [B, n]`` receives the hub's height over the floor.  Bound to the solver
+        as ``rolling_tasks`` only when the loaded library has the symbol: ``hasattr(solver, "rolling_tasks")`` is how the
+        routes ask (a library without it serves the host route)."""
+        n = len(slots)
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        k = np.ascontiguousarray(kinds, dtype=np.int32)
+        r = np.ascontiguousarray(radii, dtype=np.float64)
+        self._check(self._lib.pinkhip_rolling_tasks_device(self._h, ctypes.c_void_p(model), B, q, n, s.ctypes.data, k.ctypes.data,
+                                                           r.ctypes.data, e, sE, J, sJ, int(row0), height_out))
 
     def step_kernel(self, model: int, B: int, args) -> None:
         """Whole control step around the solve in one launch (``pinkhip_step_device``)."""

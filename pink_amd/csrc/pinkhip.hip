@@ -22,6 +22,7 @@
 #include "ik_kinematics.h"
 #include "ik_com.h"
 #include "ik_manip.h"
+#include "ik_rolling.h"
 #include "ik_rollout.h"
 #include "host_tables.h"
 #include "model_tables.h"
@@ -761,6 +762,31 @@ int pinkhip_manipulability_task_device(pinkhip_handle *h, const pinkhip_model *m
     hipLaunchKernelGGL(pinkhip::ik_manipulability_task_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
   } else {
     hipLaunchKernelGGL(pinkhip::ik_manipulability_task_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
+  }
+  PH_HIP(h, hipGetLastError());
+  return PINKHIP_OK;
+}
+
+int pinkhip_rolling_tasks_device(pinkhip_handle *h, const pinkhip_model *m, int64_t B, const double *q, int32_t n,
+                                 const int32_t *slot, const int32_t *kind, const double *radius, double *e, int64_t sE,
+                                 double *J, int64_t sJ, int32_t row0, double *height_out) {
+  if (!h || !m) return fail(h, PINKHIP_E_INVALID, "null handle / model");
+  pinkhip::RollingArgs a{m->dev, B, q, 0, {}, {}, {}, e, J, sE, sJ, row0, height_out};
+  if (const char *bad = pinkhip::rolling_set_wheels(a, n, slot, kind, radius)) return fail(h, PINKHIP_E_INVALID, bad);
+  int code = PINKHIP_E_INVALID;
+  const int *root_joint = reinterpret_cast<const int *>(m->image.bytes.data() + m->image.off_root_joint);
+  if (const char *bad = pinkhip::rolling_task_fault(a, root_joint, code)) return fail(h, code, bad);
+  if (B == 0) return PINKHIP_OK;
+  PH_HIP(h, hipSetDevice(h->device));
+  const int per = pinkhip::com_lds_doubles(m->dev.nj);
+  const dim3 block(pinkhip::kWave);
+  const int width = pinkhip::rolling_group_width(m->dev.nj);  // (lane = joint only: nv does not widen the group)
+  if (width == 8) {
+    hipLaunchKernelGGL(pinkhip::ik_rolling_tasks_kernel<8>, dim3((unsigned)((B + 7) / 8)), block, 8 * 8 * per + 16, h->stream, a);
+  } else if (width == 32) {
+    hipLaunchKernelGGL(pinkhip::ik_rolling_tasks_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
+  } else {
+    hipLaunchKernelGGL(pinkhip::ik_rolling_tasks_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
   }
   PH_HIP(h, hipGetLastError());
   return PINKHIP_OK;

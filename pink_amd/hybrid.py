@@ -27,12 +27,15 @@ from .exceptions import PinkError
 
 MAX_FRAME_TASKS = 16
 MAX_MANIPULABILITY_TASKS = 4
+MAX_WHEELS = 8  # include/pinkhip.h: PINKHIP_MAX_WHEELS
 
 
 def plan(kin_model, slots: Sequence, constraints) -> Optional[List[int]]:
     """Indices of the FrameTask slots when the hybrid route serves this stack, else ``None``: at least one FrameTask,
     at most one ComTask on a model that carries mass (two or more: the host evaluates them), at most four
-    ManipulabilityTask slots (each with one frame, mask, reference frame and rate for the whole batch), every other task of a
+    ManipulabilityTask slots (each with one frame, mask, reference frame and rate for the whole batch), at most eight
+    RollingTask / OmniwheelTask slots (each with one class, hub, floor, radius, gain, cost and lm_damping for the whole batch),
+    every other task of a
     class whose batched evaluator yields a diagonal term; equality constraints (slots of ``constraints=``) made of
     FrameTasks / RelativeFrameTasks."""
     from .tasks.com_task import ComTask
@@ -72,8 +75,14 @@ def plan(kin_model, slots: Sequence, constraints) -> Optional[List[int]]:
     for k in manips:  # (a per-instance list that differs in frame / mask / reference frame / rate / gain / cost: the host route, as frame slots)
         if any(type(t) is not ManipulabilityTask for t in slots[k]) or not be.manipulability_slot_is_uniform(slots[k], with_weights=True):
             return None
+    wheels = rolling_slots(slots)
+    if len(wheels) > MAX_WHEELS or (wheels and len(kin_model.joints) > 64):
+        return None
+    for k in wheels:  # (a per-instance list that differs in class / hub / floor / radius / gain / cost: the host route)
+        if not be.rolling_slot_is_uniform(slots[k], with_weights=True):
+            return None
     for k, col in enumerate(slots):
-        if k not in frames and k not in coms and k not in manips and type(col[0]) not in (PostureTask, DampingTask, LowAccelerationTask, JointVelocityTask):
+        if k not in frames and k not in coms and k not in manips and k not in wheels and type(col[0]) not in (PostureTask, DampingTask, LowAccelerationTask, JointVelocityTask):
             return None
     return frames
 
@@ -92,6 +101,22 @@ def manipulability_slots(slots: Sequence) -> List[int]:
     return [k for k, col in enumerate(slots) if type(col[0]) is ManipulabilityTask]
 
 
+def rolling_slots(slots: Sequence) -> List[int]:
+    """Indices of the RollingTask / OmniwheelTask slots of a stack, in stack order."""
+    from .tasks.rolling_task import OmniwheelTask, RollingTask
+
+    return [k for k, col in enumerate(slots) if type(col[0]) in (RollingTask, OmniwheelTask)]
+
+
+def wheel_tables(tasks) -> tuple:
+    """``(frames, kinds, radii)`` of the wheels ``tasks`` for ``pinkhip_rolling_tasks_device``: the ``(hub, floor)`` pairs that
+    become the relative slots of a device model, 0 (rolling) / 1 (omniwheel), and the radii."""
+    from .tasks.rolling_task import OmniwheelTask
+
+    return (tuple((t.hub_frame, t.floor_frame) for t in tasks), [1 if type(t) is OmniwheelTask else 0 for t in tasks],
+            [float(t.wheel_radius) for t in tasks])
+
+
 class HybridState:
     """Device buffers and model tables of one call shape (kept by :func:`pink_amd.solve_ik.solve_ik_batch` like the
     device-resident states)."""
@@ -106,6 +131,7 @@ class HybridState:
         self.cframes, self.carrays, self.cmodel = None, None, None  # device model of the equality constraints' frames
         self.dcom, self.com_key = None, None  # device copy of the model's mass tables (a ComTask slot)
         self.mframes, self.marrays, self.mmodel = None, None, None  # device model of the ManipulabilityTask slots' frames
+        self.rframes, self.rarrays, self.rmodel = None, None, None  # device model of the wheels' (hub, floor) slots
 
     def com_tables(self) -> int:
         """The device mass tables of the model as it is NOW (an edit of a mass or a centre builds them anew)."""
@@ -132,6 +158,20 @@ class HybridState:
             self.mmodel = self.api.model_create(self.marrays.desc)
             self.mframes = frames
         return self.mmodel
+
+    def rolling_model(self, frames) -> int:
+        """Device model whose slots are the ``(hub, floor)`` pairs of the RollingTask / OmniwheelTask slots: relative slots,
+        frame = hub, root = floor."""
+        frames = tuple(frames)
+        if self.rframes != frames:
+            from .rollout import ModelArrays
+
+            if self.rmodel is not None:
+                self.api.model_destroy(self.rmodel)
+            self.rarrays = ModelArrays(self.model, list(frames))
+            self.rmodel = self.api.model_create(self.rarrays.desc)
+            self.rframes = frames
+        return self.rmodel
 
     def constraint_model(self, frames) -> int:
         frames = tuple(frames)
@@ -167,6 +207,9 @@ class HybridState:
         if self.mmodel is not None:
             self.api.model_destroy(self.mmodel)
             self.mmodel = None
+        if self.rmodel is not None:
+            self.api.model_destroy(self.rmodel)
+            self.rmodel = None
         self.api.model_destroy(self.dmodel)
 
 
@@ -185,7 +228,11 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     km = manipulability_slots(slots)
     mcols = [slots[k] for k in km]
     nm = len(mcols)
-    diag = [be.task_term(kq, col, None) for k, col in enumerate(slots) if k not in frame_slots and k != kc and k not in km]
+    kr = rolling_slots(slots)
+    rcols = [slots[k] for k in kr]
+    rwidths = [len(col[0].rows) for col in rcols]
+    nr = sum(rwidths)
+    diag = [be.task_term(kq, col, None) for k, col in enumerate(slots) if k not in frame_slots and k != kc and k not in km and k not in kr]
     if any(not isinstance(t, DiagonalTaskTerm) for t in diag):
         raise PinkError("hybrid route: a task outside the FrameTasks produced a dense Jacobian")
     lb = np.full((B, nv), -np.inf)
@@ -214,15 +261,22 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     # ... and one dense task of one row per ManipulabilityTask slot behind those
     for col in mcols:
         be._check_slot(col)
-    Kd = 6 * nf + 3 * nc + nm
+    # ... and one dense task of three (Rolling) or two (Omniwheel) rows per wheel slot behind those
+    for col in rcols:
+        be._check_slot(col)
+    Kd = 6 * nf + 3 * nc + nm + nr
     K = Kd + b0.K
     fcost = [be._costs(col, 6) for col in fcols]
-    widths = [6] * nf + [3] * nc + [1] * nm
+    widths = [6] * nf + [3] * nc + [1] * nm + rwidths
     if ccol is not None:
         fcost.append(be._costs(ccol, 3))
         fcols = fcols + [ccol]
     for col in mcols:
         fcost.append(be._costs(col, 1))
+        fcols = fcols + [col]
+    for col, w in zip(rcols, rwidths):
+        c = be._costs(col, w)
+        fcost.append(1.0 if c is None else c)  # (cost=None: identity weights, pink/tasks/task.py:148-156)
         fcols = fcols + [col]
     batched = b0.cost.ndim == 2 or any(np.ndim(c) == 2 for c in fcost)
     if batched:
@@ -237,15 +291,16 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     targets = np.ascontiguousarray(np.stack([_targets_of(col, B) for col in fcols[:nf]], axis=1))  # [B, nf, 12]
     i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)  # noqa: E731
     f64 = lambda v: np.ascontiguousarray(v, dtype=np.float64)  # noqa: E731
+    nw = len(rcols)
     task_rows = i32([6 * i for i in range(nf + 1)] + [6 * nf + 3] * nc + [6 * nf + 3 * nc + i + 1 for i in range(nm)]
-                    + [Kd + int(r) for r in b0.task_rows[1:]])
-    task_kind = i32([0] * (nf + nc + nm) + list(b0.task_kind))
-    task_col0 = i32([0] * (nf + nc + nm) + list(b0.task_col0))
+                    + [6 * nf + 3 * nc + nm + int(r) for r in np.cumsum(rwidths)] + [Kd + int(r) for r in b0.task_rows[1:]])
+    task_kind = i32([0] * (nf + nc + nm + nw) + list(b0.task_kind))
+    task_col0 = i32([0] * (nf + nc + nm + nw) + list(b0.task_col0))
     gain = f64([col[0].gain for col in fcols] + list(b0.gain))
     lm = f64([col[0].lm_damping for col in fcols] + list(b0.lm_damping))
     brow, bsafe = i32(b0.barrier_rows), f64(b0.barrier_safe_gain if b0.barrier_safe_gain.size else [0.0])
     d = Desc()
-    d.B, d.nv, d.T, d.Kd, d.K, d.md, d.n_eq = B, nv, nf + nc + nm + len(diag), Kd, K, b0.md, n_eq
+    d.B, d.nv, d.T, d.Kd, d.K, d.md, d.n_eq = B, nv, nf + nc + nm + nw + len(diag), Kd, K, b0.md, n_eq
     d.task_rows, d.task_kind, d.task_col0 = (a.ctypes.data_as(c_int32_p) for a in (task_rows, task_kind, task_col0))
     d.gain, d.lm_damping = gain.ctypes.data_as(c_double_p), lm.ctypes.data_as(c_double_p)
     d.n_barriers = int(b0.barrier_safe_gain.size)
@@ -284,6 +339,9 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
             t0 = col[0]
             api.manipulability_task(mmodel, B, d_q, i, int(t0.reference_frame), t0.row_mask, float(t0.manipulability_rate), d_e, K,
                                     d_J, Kd * nv, 6 * nf + 3 * nc + i)
+    if nw:  # the rows of all wheels behind the manipulability rows, ONE launch: the world poses are composed once
+        frames, kinds, radii = wheel_tables([col[0] for col in rcols])
+        api.rolling_tasks(s.rolling_model(frames), B, d_q, list(range(nw)), kinds, radii, d_e, K, d_J, Kd * nv, 6 * nf + 3 * nc + nm)
     if n_eq:
         # the same kernel on the constraints' frames, writing J into the leading rows of Gd and e into those of hd (row
         # pitches md nv and md); hd then becomes -gain e on the host: [B, md] doubles go home and back

@@ -175,6 +175,17 @@ class BatchKinematics:
         Rf, _ = self.frame_pose(frame)
         return Rf @ self.frame_jacobian(frame)[:, :3]
 
+    def rolling_rows(self, hub_frame: str, floor_frame: str, wheel_radius: float) -> Tuple[np.ndarray, np.ndarray]:
+        """``(z [B], J [B, 3, nv])`` of a wheel (``pink_amd/tasks/rolling_task.py``): height of the hub over the floor's
+        plane, and the velocity of the contact point ``p_H - rho R_F e_z`` carried by the hub's body, in the floor's axes.
+        The floor is taken as inertial: only the hub's ancestors own columns."""
+        RF, pF = self.frame_pose(floor_frame)
+        _, pH = self.frame_pose(hub_frame)
+        n = RF[:, :, 2]
+        z = np.einsum("bi,bi->b", n, pH - pF)
+        hub = self.model.frames[self.model.getFrameId(hub_frame)].joint
+        return z, self._jacobian_at(RF, pH - wheel_radius * n, hub, rotate=True)[:, :3]
+
     def joint_jacobian_world_aligned(self, joint: int) -> np.ndarray:
         """``pin.getJointJacobian(..., LOCAL_WORLD_ALIGNED)`` of joint ``joint``: ``[B, 6, nv]``."""
         return self._jacobian_at(self.R[:, joint], self.p[:, joint], joint, rotate=False)

@@ -192,8 +192,15 @@ class DeviceRollout:
                  position_barriers: Sequence = (), floating_base_limit=None, const_tasks: Sequence = (),
                  diag_tasks: Sequence = (), acceleration_limit: Optional[np.ndarray] = None,
                  velocity_limit: Optional[np.ndarray] = None, constraint_slots: Sequence = (), warm_start: bool = False,
-                 com_task=None, manipulability_tasks: Sequence = ()):
-        """``manipulability_tasks``: up to four :class:`pink_amd.tasks.ManipulabilityTask` (``pink/tasks/manipulability_task.py``)
+                 com_task=None, manipulability_tasks: Sequence = (), rolling_tasks: Sequence = ()):
+        """``rolling_tasks``: up to eight :class:`pink_amd.tasks.RollingTask` / :class:`~pink_amd.tasks.OmniwheelTask`
+        (``pink/tasks/rolling_task.py``, ``omniwheel_task.py``) whose three / two rows each ``pinkhip_rolling_tasks_device`` forms
+        behind the FrameTask, ComTask and ManipulabilityTask rows, from the configuration the step solves at, all wheels in one
+        launch (``fused=True``: step kernel, rolling kernel, solve; ``fused=False``: one more launch in front of the solve).
+        The whole-step kernel does not form these rows: ``fused="kernel"`` raises.  :meth:`wheel_heights` returns the hubs'
+        heights over their floors.
+
+        ``manipulability_tasks``: up to four :class:`pink_amd.tasks.ManipulabilityTask` (``pink/tasks/manipulability_task.py``)
         whose one row each ``pinkhip_manipulability_task_device`` forms behind the FrameTask and ComTask rows, from the
         configuration the step solves at (``fused=True``: step kernel, one launch per task, solve; ``fused=False``: the same
         launches in front of the solve).  The whole-step kernel does not form these rows: ``fused="kernel"`` raises.
@@ -264,6 +271,20 @@ class DeviceRollout:
                 raise ValueError("manipulability rows on the device need a model of at most 64 joints")
             for t in self.manip_tasks:
                 check_revolute_path(model, t.frame)
+        self.wheel_tasks, self.rmodel, self.d_heights = list(rolling_tasks), None, None
+        if self.wheel_tasks:
+            from .tasks.rolling_task import OmniwheelTask, RollingTask
+
+            if self.fused == "kernel":
+                raise ValueError('the whole-step kernel does not form wheel-contact rows: a RollingTask / OmniwheelTask needs fused=True or fused=False')
+            if not hasattr(api, "rolling_tasks"):
+                raise ValueError("this solver has no pinkhip_rolling_tasks_device: a RollingTask / OmniwheelTask needs it")
+            if len(self.wheel_tasks) > 8 or any(type(t) not in (RollingTask, OmniwheelTask) for t in self.wheel_tasks):
+                raise ValueError("rolling_tasks: at most eight RollingTask / OmniwheelTask objects")
+            if len(model.joints) > 64:
+                raise ValueError("wheel-contact rows on the device need a model of at most 64 joints")
+            for t in self.wheel_tasks:  # (an unknown frame: what a FrameTask raises)
+                model.getFrameId(t.hub_frame), model.getFrameId(t.floor_frame)
         # (a frame task (frame, ...) regulates the frame in the world; ((frame, root), ...) the pose of frame in root --
         # a RelativeFrameTask, pink/tasks/relative_frame_task.py: a relative slot of the device model)
         self.arrays = ModelArrays(model, [ft[0] for ft in frame_tasks], velocity_limit=velocity_limit)
@@ -292,7 +313,8 @@ class DeviceRollout:
             raise ValueError("constant-row tasks must share one reference configuration q_0")
         self.n_com = 3 if com_task is not None else 0
         self.n_manip = len(self.manip_tasks)
-        self.Kd = 6 * nf + self.n_crow + self.n_com + self.n_manip  # (n_crow = 0 beside these: constant-row tasks need fused="kernel")
+        self.n_wheel_rows = sum(len(t.rows) for t in self.wheel_tasks)
+        self.Kd = 6 * nf + self.n_crow + self.n_com + self.n_manip + self.n_wheel_rows  # (n_crow = 0 beside these: constant-row tasks need fused="kernel")
         n_post = nv - root_nv if posture_cost is not None else 0
         self.K = self.Kd + n_post + sum(e.shape[0] for _, e, *_ in diag_tasks)
         # task tables of the QP (include/pinkhip.h: frame tasks, constant-row tasks, then the diagonal ones: the posture first)
@@ -310,6 +332,10 @@ class DeviceRollout:
         for t in self.manip_tasks:  # one dense row each behind the centre-of-mass rows
             rows.append(rows[-1] + 1), kind.append(0), col0.append(0), gain.append(float(t.gain)), lm.append(float(t.lm_damping))
             cost.append(float(1.0 if t.cost is None else t.cost))
+        for t in self.wheel_tasks:  # three or two dense rows each behind the manipulability rows
+            w = len(t.rows)
+            rows.append(rows[-1] + w), kind.append(0), col0.append(0), gain.append(float(t.gain)), lm.append(float(t.lm_damping))
+            cost += list(np.broadcast_to(np.asarray(1.0 if t.cost is None else t.cost, float), (w,)))
         if n_post:
             rows.append(rows[-1] + n_post), kind.append(1), col0.append(root_nv), gain.append(posture_gain), lm.append(posture_lm_damping)
             cost += [float(posture_cost)] * n_post
@@ -455,6 +481,13 @@ class DeviceRollout:
             self.marrays = ModelArrays(model, [t.frame for t in self.manip_tasks])  # (kept: the descriptor points into its arrays)
             self.mmodel = a.model_create(self.marrays.desc)
             self.d_manip = f8(B, self.n_manip)
+        if self.wheel_tasks:  # (a device model of its own: its slots are the wheels' (hub, floor) pairs, relative slots)
+            from .hybrid import wheel_tables
+
+            frames, self.wheel_kinds, self.wheel_radii = wheel_tables(self.wheel_tasks)
+            self.rarrays = ModelArrays(model, list(frames))  # (kept: the descriptor points into its arrays)
+            self.rmodel = a.model_create(self.rarrays.desc)
+            self.d_heights = f8(B, len(self.wheel_tasks))
         if self.warm_start:  # one byte per robot and tangent coordinate, read and written in place by every step
             self.d_active = a.alloc(B * nv)
             a.put(self.d_active, np.zeros(B * nv, dtype=np.uint8))
@@ -685,6 +718,26 @@ class DeviceRollout:
                                          self.d_e, self.K, self.d_J, self.Kd * self.nv, row0 + i,
                                          self.d_manip + 8 * self.B * i if m_out else None)
 
+    def _wheel_rows(self, heights: bool = False) -> None:
+        """The RollingTask / OmniwheelTask rows of the configurations in ``d_q``, behind the frame, centre-of-mass and
+        manipulability rows: one launch for all wheels."""
+        n = len(self.wheel_tasks)
+        self.api.rolling_tasks(self.rmodel, self.B, self.d_q, list(range(n)), self.wheel_kinds, self.wheel_radii, self.d_e, self.K,
+                               self.d_J, self.Kd * self.nv, 6 * len(self.frames) + self.n_com + self.n_manip,
+                               self.d_heights if heights else None)
+
+    def wheel_heights(self) -> np.ndarray:
+        """``[B, n_wheels]``: heights of the hubs over their floors' planes at the current configurations, computed on the
+        device."""
+        if not self.wheel_tasks:
+            raise ValueError("this rollout has no RollingTask / OmniwheelTask")
+        self.flush()
+        self._wheel_rows(heights=True)  # (the rows it writes are formed anew by every step)
+        self.api.sync()
+        z = np.zeros((self.B, len(self.wheel_tasks)))
+        self.api.get(z, self.d_heights)
+        return z
+
     def manipulability(self) -> np.ndarray:
         """``[n_tasks, B]``: manipulability indices of the current configurations, computed on the device."""
         if not self.manip_tasks:
@@ -747,6 +800,8 @@ class DeviceRollout:
                 self._com_rows()
             if self.manip_tasks:
                 self._manip_rows()
+            if self.wheel_tasks:
+                self._wheel_rows()
             a.solve_raw(self.desc, self.problem, self.result)
             self._pending = bool(integrate)
         else:  # one launch for FK, one per FrameTask, limits + posture, solve, integrate
@@ -761,6 +816,8 @@ class DeviceRollout:
                 self._com_rows()
             if self.manip_tasks:
                 self._manip_rows()
+            if self.wheel_tasks:
+                self._wheel_rows()
             a.solve_raw(self.desc, self.problem, self.result)
             if integrate:
                 a.integrate_checked(self.dmodel, B, self.d_q, self.d_dq, self.d_status, self.d_fail, self.steps_done)
@@ -1066,7 +1123,10 @@ class DeviceRollout:
         if getattr(self, "mmodel", None) is not None:
             self.api.model_destroy(self.mmodel)
             self.mmodel = None
-        for name in ("d_com", "d_com_target", "d_manip"):
+        if getattr(self, "rmodel", None) is not None:
+            self.api.model_destroy(self.rmodel)
+            self.rmodel = None
+        for name in ("d_com", "d_com_target", "d_manip", "d_heights"):
             if getattr(self, name, None) is not None:
                 self.api.release(getattr(self, name))
                 setattr(self, name, None)

@@ -493,6 +493,10 @@ def _device_kinematics_plan(configurations, tasks, limits, barriers, constraints
 
     if any(isinstance(t, ManipulabilityTask) for t in flat):
         return _declined("ManipulabilityTask: the whole-step kernel does not form its row (the hybrid route does)")
+    from .tasks.rolling_task import RollingTask
+
+    if any(isinstance(t, RollingTask) for t in flat):
+        return _declined("RollingTask / OmniwheelTask: the whole-step kernel does not form wheel-contact rows (the hybrid route does)")
     plan = _device_kinematics_plan_tasks(configurations, tasks)
     if plan is None:
         return _declined("a task the whole-step kernel does not form (FrameTask / RelativeFrameTask, one PostureTask, table-formed tasks shared by the batch)")
@@ -1090,6 +1094,8 @@ def _solve_hybrid(configurations, tasks, dt, damping, limits, barriers, constrai
         return None
     if hybrid.manipulability_slots(slots) and not hasattr(api, "manipulability_task"):  # (a solver without the manipulability kernel)
         return None
+    if hybrid.rolling_slots(slots) and not hasattr(api, "rolling_tasks"):  # (a solver without the wheel-contact kernel)
+        return None
     if limits is None:  # model defaults, pink/solve_ik.py:94-105
         model.ensure_limits()
         limits = [model.configuration_limit, model.velocity_limit]
@@ -1135,7 +1141,7 @@ def _record_stats(result, route: str) -> None:
 
 def last_solve_stats() -> dict:
     """What the last :func:`solve_ik_batch` call of this process did: ``route`` (``"device"``: kinematics, rows and QP
-    formed on the device from ``q``; ``"hybrid"``: FrameTask rows (and one ComTask's, up to four ManipulabilityTasks') formed on the device from ``q``, the other tasks /
+    formed on the device from ``q``; ``"hybrid"``: FrameTask rows (and one ComTask's, up to four ManipulabilityTasks', up to eight RollingTasks' / OmniwheelTasks') formed on the device from ``q``, the other tasks /
     limits / barriers evaluated on the host, QP on the device; ``"host-evaluated"``: everything evaluated on the host,
     QP on the device), ``instances``, ``failed``, ``iters_mean`` and ``paths`` -- the share of the batch per solver path
     (:meth:`pink_amd.batch_solver.BatchResult.path_fractions`; ``handover`` is the share that paid for both solvers)."""

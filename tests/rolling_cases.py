@@ -1,0 +1,379 @@
+"""Models, configurations, the 60-digit reference and the emulator binding of the RollingTask / OmniwheelTask tests
+(tests/test_rolling_task.py, test_rolling_device.py, test_rolling_routes.py, test_rolling_golden.py): computed once per
+session, shared by all of them.
+
+  cart    prismatic -> revolute -> prismatic -> wheel revolute (nj = 4: eight robots per wavefront); one RollingTask; the
+          floor hangs on the world with a tilted, offset placement
+  biped   free-flyer + 2 x (hip, knee, wheel), nj = 7, nv = 12 (still eight robots per wavefront: one lane per JOINT); one
+          Rolling, one Omniwheel; the floor of the first is the world frame at identity, the other's is tilted
+  quad    free-flyer + 4 x 3 joints, nj = 13 (two robots per wavefront); four wheels, kinds mixed (3 + 2 + 3 + 2 = 10 rows);
+          the hub of wheel 2 sits on a knee, so the joint below it on the same leg is off its path
+  tree34  the 34-joint tree with free-flyer of tests/com_task_cases.py (one robot per wavefront); two wheels on leaves of
+          unequal depth; the floor of the second hangs on a moving joint of another branch
+
+Magnitudes -- a condition, not a taste.  Hub frames carry a placement that is not the identity, radii lie in [0.05, 0.3]
+beside link lengths of 0.3, floors are tilted by at least 0.3 rad, revolute joints make several turns, prismatic ones move
+by +-0.5, free-flyer quaternions have w < 0.  With these every term of the rows -- rho in the contact point, R_F, the path
+mask, the row choice of the Omniwheel, the sign of rho, the columns the floor's ancestors do NOT get -- moves the rows by
+far more than the bar: :func:`term_moves` drops each term from the 60-digit rows, without any kernel, and
+tests/test_rolling_task.py::test_every_term_is_worth_100_bars holds the change to at least 100 bars on every instance of
+every model the term applies to.
+"""
+import ctypes
+import functools
+import json
+import os
+
+import mpmath as mp
+import numpy as np
+
+from oracle import exact_kinematics as ek
+from pink_amd._lib import PinkHipError
+from pink_amd.configuration import Model
+from pink_amd.lie import SE3, exp3
+from pink_amd.rollout import ModelArrays
+from pink_amd.tasks import OmniwheelTask, RollingTask
+from tests.com_task_cases import tree
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EPS = 2.0 ** -52
+K_ROLL = 8.0  # the bar tests/test_kinematics_exact.py holds poses and body Jacobians to
+ROLLING, OMNI = 0, 1
+HUB = SE3(exp3([0.2, -0.3, 0.25]), [0.02, -0.03, 0.04])  # placement of a hub frame on its joint
+TILT = SE3(exp3([0.35, -0.4, 0.2]), [0.3, -0.2, 0.1])  # a tilted floor (0.57 rad) with an offset
+
+
+def _cart():
+    m = Model()
+    a = m.add_joint("slide_x", "prismatic", -1, SE3(exp3([0.1, 0.2, -0.1]), [0.0, 0.1, 0.2]), [1.0, 0.1, 0.0], -1.0, 1.0, 2.0)
+    b = m.add_joint("yaw", "revolute", a, SE3(exp3([0.0, 0.3, 0.1]), [0.3, 0.0, 0.0]), [0.1, 0.0, 1.0], -7.0, 7.0, 2.0)
+    c = m.add_joint("lift", "prismatic", b, SE3(exp3([-0.2, 0.0, 0.3]), [0.0, 0.3, 0.0]), [0.0, 0.2, 1.0], -1.0, 1.0, 2.0)
+    d = m.add_joint("wheel", "revolute", c, SE3(exp3([0.3, 0.1, 0.0]), [0.0, 0.0, -0.3]), [0.0, 1.0, 0.1], -7.0, 7.0, 2.0)
+    m.add_frame("hub", d, HUB)
+    m.add_frame("floor", -1, TILT)
+    return m, [(ROLLING, "hub", "floor", 0.12)]
+
+
+def _leg(m, root, name, offset, seed, n=3):
+    rng = np.random.default_rng(seed)
+    ids, parent = [], root
+    for i in range(n):
+        pl = SE3(exp3(0.5 * rng.normal(size=3)), np.asarray(offset, dtype=float) if i == 0 else 0.3 * rng.normal(size=3) / np.sqrt(3))
+        parent = m.add_joint(f"{name}_{('hip', 'knee', 'wheel')[i]}", "revolute", parent, pl, rng.normal(size=3), -7.0, 7.0, 2.0)
+        ids.append(parent)
+    return ids
+
+
+def _biped():
+    m = Model()
+    root = m.add_joint("root_joint", "free_flyer")
+    left = _leg(m, root, "left", [0.0, 0.15, -0.1], 1)
+    right = _leg(m, root, "right", [0.0, -0.15, -0.1], 2)
+    m.add_frame("left_hub", left[2], HUB)
+    m.add_frame("right_hub", right[2], SE3(exp3([-0.3, 0.1, 0.2]), [0.01, 0.04, -0.02]))
+    m.add_frame("base", root, SE3(exp3([0.1, 0.0, 0.2]), [0.05, 0.0, 0.1]))
+    m.add_frame("world", -1, SE3())
+    m.add_frame("ramp", -1, TILT)
+    return m, [(ROLLING, "left_hub", "world", 0.1), (OMNI, "right_hub", "ramp", 0.07)]
+
+
+def _quad():
+    m = Model()
+    root = m.add_joint("root_joint", "free_flyer")
+    legs = [_leg(m, root, f"leg{i}", [0.2 * (1 - 2 * (i // 2)), 0.15 * (1 - 2 * (i % 2)), -0.05], 10 + i) for i in range(4)]
+    for i, leg in enumerate(legs):
+        on = leg[1] if i == 2 else leg[2]  # (wheel 2: on the knee -- the wheel joint below it is off its path)
+        m.add_frame(f"hub{i}", on, SE3(exp3([0.1 * (i + 1), -0.2, 0.15]), [0.03, 0.01 * i, -0.02]))
+    m.add_frame("base", root, SE3())
+    m.add_frame("ground", -1, SE3(exp3([0.3, 0.1, 0.0]), [0.0, 0.0, -0.4]))
+    m.add_frame("ramp", -1, TILT)
+    return m, [(ROLLING, "hub0", "ground", 0.05), (OMNI, "hub1", "ramp", 0.3), (ROLLING, "hub2", "ramp", 0.15), (OMNI, "hub3", "ground", 0.2)]
+
+
+def _depth(m, k):
+    d = 0
+    while k >= 0:
+        d, k = d + 1, m.joints[k].parent
+    return d
+
+
+def _ancestors(m, k):
+    out = set()
+    while k >= 0:
+        out.add(k)
+        k = m.joints[k].parent
+    return out
+
+
+def _tree34():
+    m = tree(33, True, 12)
+    nj = len(m.joints)
+    leaves = [k for k in range(nj) if all(j.parent != k for j in m.joints)]
+    leaves.sort(key=lambda k: (_depth(m, k), k))
+    shallow, deep = leaves[0], leaves[-1]
+    assert _depth(m, shallow) < _depth(m, deep)
+    # a moving joint of another branch: not an ancestor of the deep leaf, not the root, and the deep leaf is not below it
+    other = next(k for k in range(nj - 1, 0, -1) if k not in _ancestors(m, deep) and k not in _ancestors(m, shallow) and _depth(m, k) >= 3)
+    m.add_frame("hub_a", shallow, HUB)
+    m.add_frame("hub_b", deep, SE3(exp3([-0.3, 0.1, 0.2]), [0.01, 0.04, -0.02]))
+    m.add_frame("ramp", -1, TILT)
+    m.add_frame("deck", other, SE3(exp3([0.3, 0.3, -0.2]), [0.1, 0.0, -0.1]))  # a floor that moves with q
+    return m, [(OMNI, "hub_a", "ramp", 0.25), (ROLLING, "hub_b", "deck", 0.08)]
+
+
+@functools.lru_cache(maxsize=None)
+def models():
+    """name -> (model, wheels); a wheel is (kind, hub frame, floor frame, radius)."""
+    return {"cart": _cart(), "biped": _biped(), "quad": _quad(), "tree34": _tree34()}
+
+
+BATCH = {"cart": 11, "biped": 11, "quad": 3, "tree34": 2}
+WIDTH = {"cart": 8, "biped": 8, "quad": 32, "tree34": 64}  # lanes per robot: the smallest of 8 / 32 / 64 that holds nj
+
+
+def tasks_of(name, cost=1.0, **kw):
+    return [(OmniwheelTask if k == OMNI else RollingTask)(hub, floor, r, cost, **kw) for k, hub, floor, r in models()[name][1]]
+
+
+def arrays(name):
+    """Device model tables whose slots are the wheels' (hub, floor) pairs."""
+    model, wheels = models()[name]
+    return ModelArrays(model, [(hub, floor) for _, hub, floor, _ in wheels])
+
+
+def rows_of(kinds):
+    return sum(2 if k == OMNI else 3 for k in kinds)
+
+
+def configurations(name, B=None, seed=7):
+    """As tests/com_task_cases.configurations: revolute angles over a few turns, prismatic coordinates in +-0.5, free-flyer
+    quaternions with w < 0."""
+    model = models()[name][0]
+    B = BATCH[name] if B is None else B
+    rng = np.random.default_rng(seed + len(name))
+    q = np.zeros((B, model.nq))
+    for j in model.joints:
+        if j.kind == "free_flyer":
+            q[:, j.idx_q:j.idx_q + 3] = rng.normal(size=(B, 3))
+            qu = rng.normal(size=(B, 4))
+            qu[:, 3] = -np.abs(qu[:, 3]) - 0.1
+            q[:, j.idx_q + 3:j.idx_q + 7] = qu / np.linalg.norm(qu, axis=1, keepdims=True)
+        elif j.kind == "prismatic":
+            q[:, j.idx_q] = rng.uniform(-0.5, 0.5, size=B)
+        else:
+            q[:, j.idx_q] = rng.uniform(-6.0, 6.0, size=B)
+    return q
+
+
+# ---- the 60-digit reference ---------------------------------------------------------------------------------------------
+def _cross(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def _pose_of(oM, joint, placement12):
+    P = ek.pose_matrix(placement12)
+    return P if joint < 0 else ek.mm(oM[joint], P)
+
+
+TERMS = ("pc_is_ph", "no_RF", "no_mask", "omni_01", "rho_sign", "floor_ancestors")
+
+
+@ek.precise
+def exact_rows(t, q, kinds, radii, drop=None):
+    """(e [nr], J [nr][nv], z [n]) as mpf from the exact joint poses (oracle.exact_kinematics) by plain mpf products.  ``t``:
+    model tables with one relative slot per wheel.  ``drop``: one of TERMS -- the rows with that term of the geometry left
+    out (what a wrong kernel would form; :func:`term_moves`)."""
+    oM = ek.joint_poses(t, q)
+    nj = len(t.parent)
+    nv = sum(6 if int(x) == ek.FREE_FLYER else 1 for x in t.jtype)
+    e, J, zs = [], [], []
+    for w, kind in enumerate(kinds):
+        rho = mp.mpf(float(radii[w]))
+        if drop == "rho_sign":
+            rho = -rho
+        fj, rj = int(t.frame_joint[w]), int(t.frame_root_joint[w])
+        TH, TF = _pose_of(oM, fj, t.frame_placement[w]), _pose_of(oM, rj, t.frame_root_placement[w])
+        n = [TF[i][2] for i in range(3)]
+        pH, pF = [TH[i][3] for i in range(3)], [TF[i][3] for i in range(3)]
+        z = sum(n[i] * (pH[i] - pF[i]) for i in range(3))
+        pC = pH if drop == "pc_is_ph" else [pH[i] - rho * n[i] for i in range(3)]
+        path, k = set(), fj
+        while k >= 0:
+            path.add(k)
+            k = int(t.parent[k])
+        if drop == "floor_ancestors":
+            k = rj
+            while k >= 0:
+                path.add(k)
+                k = int(t.parent[k])
+        if drop == "no_mask":
+            path = set(range(nj))
+        Jw = [[mp.mpf(0)] * nv for _ in range(3)]
+        for k in sorted(path):
+            jt, iv = int(t.jtype[k]), int(t.idx_v[k])
+            Rk = [[oM[k][i][j] for j in range(3)] for i in range(3)]
+            d = [pC[i] - oM[k][i][3] for i in range(3)]
+            if jt == ek.FREE_FLYER:
+                axes = [[Rk[i][c] for i in range(3)] for c in range(3)]
+                cols = axes + [_cross(s, d) for s in axes]
+            else:
+                a = [mp.mpf(float(c)) for c in t.axis[k]]
+                u = [sum(Rk[i][j] * a[j] for j in range(3)) for i in range(3)]
+                cols = [_cross(u, d) if jt == ek.REVOLUTE else u]
+            for c, l in enumerate(cols):
+                for r in range(3):
+                    Jw[r][iv + c] = l[r] if drop == "no_RF" else sum(TF[i][r] * l[i] for i in range(3))
+        ew = [mp.mpf(0), mp.mpf(0), z - rho]
+        keep = (0, 1, 2) if kind == ROLLING else ((0, 1) if drop == "omni_01" else (0, 2))
+        e += [ew[r] for r in keep]
+        J += [Jw[r] for r in keep]
+        zs.append(z)
+    return e, J, zs
+
+
+def _split(ref):
+    fl = ek.flat(ref)
+    hi = np.array([float(x) for x in fl])
+    with mp.workdps(ek.DPS):
+        lo = np.array([float(x - mp.mpf(h)) for x, h in zip(fl, hi)])
+    return hi, lo
+
+
+def ratio(dev, ref, S):
+    """Error in units of u = S + eps max|reference| (tests/test_kinematics_exact.py)."""
+    hi, lo = ref
+    u = S + EPS * np.abs(hi).max()
+    return float(np.abs((np.asarray(dev, dtype=np.float64).ravel() - hi) - lo).max() / u)
+
+
+def _fn(arr, kinds):
+    def fn(pl, ax, qb, fp, rp, rad):
+        t = ek.tables(arr, placement=pl, axis=ax, frame_placement=fp, frame_root_joint=arr.frame_root_joint, frame_root_placement=rp)
+        return exact_rows(t, qb, kinds, rad)
+    return fn
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """q and, per instance, ((e, S_e), (J, S_J), (z, S_z)) with every exact array split into (hi, lo): S is how far the exact
+    result moves when every double it is computed from -- placements, axes, q, frame placements, radii -- moves by one ulp."""
+    _, wheels = models()[name]
+    arr = arrays(name)
+    kinds, radii = [w[0] for w in wheels], np.array([w[3] for w in wheels])
+    q = configurations(name)
+    fn = _fn(arr, kinds)
+    out = []
+    for b in range(q.shape[0]):
+        inputs = [arr.placement, arr.axis, q[b], arr.frame_placement, arr.frame_root_placement, radii]
+        base = fn(*inputs)
+        S = ek.spread(fn, inputs, draws=1, seed=b, base=base)
+        out.append(tuple((_split(base[i]), S[i]) for i in range(3)))
+    return q, out
+
+
+def worst(name, e, J, z=None):
+    """Worst ratios (e, J, z) over the batch of ``name``; J [B, nr, nv] (or flat rows), e [B, nr], z [B, n] or None."""
+    q, ref = reference(name)
+    B = q.shape[0]
+    re = max(ratio(e[b], *ref[b][0]) for b in range(B))
+    rj = max(ratio(J[b], *ref[b][1]) for b in range(B))
+    rz = 0.0 if z is None else max(ratio(z[b], *ref[b][2]) for b in range(B))
+    return re, rj, rz
+
+
+@functools.lru_cache(maxsize=None)
+def reference_bar(name):
+    """The bar of a case: K_ROLL = 8 units -- or, where the REFERENCE's own class (its fp64 rows on the anchor configurations,
+    stored by tests/golden/make_golden_rolling.py) sits above 2 units, four times the reference's ratio."""
+    path = os.path.join(ROOT, "tests", "golden", "rolling_task.npz")
+    g = np.load(path)
+    if f"{name}/anchor_q" not in g.files:
+        return K_ROLL, K_ROLL
+    q, _ = reference(name)
+    assert np.array_equal(g[f"{name}/anchor_q"], q)
+    re, rj, _ = worst(name, g[f"{name}/anchor_e"], g[f"{name}/anchor_J"])
+    note_ratios("reference", name, re, rj)
+    return (4.0 * re if re > 2.0 else K_ROLL), (4.0 * rj if rj > 2.0 else K_ROLL)
+
+
+@functools.lru_cache(maxsize=None)
+def term_moves(name):
+    """{term: the least over the instances of (largest change of an entry of e or J when the term is dropped) / (K_ROLL u)}
+    for the terms that apply to the model (a path mask needs a joint off a path, an Omniwheel row choice an Omniwheel, the
+    floor's ancestors a floor on a joint that is not among the hub's ancestors)."""
+    model, wheels = models()[name]
+    arr = arrays(name)
+    kinds, radii = [w[0] for w in wheels], np.array([w[3] for w in wheels])
+    q, ref = reference(name)
+    t = ek.tables(arr, frame_root_joint=arr.frame_root_joint, frame_root_placement=arr.frame_root_placement)
+    nj = len(model.joints)
+    hub_paths = [_ancestors(model, int(arr.frame_joint[w])) for w in range(len(wheels))]
+    applies = {
+        "pc_is_ph": True, "no_RF": True, "rho_sign": True,
+        "no_mask": any(len(p) < nj for p in hub_paths),
+        "omni_01": OMNI in kinds,
+        "floor_ancestors": any(_ancestors(model, int(arr.frame_root_joint[w])) - hub_paths[w] for w in range(len(wheels))),
+    }
+    out = {}
+    for term in TERMS:
+        if not applies[term]:
+            continue
+        least = np.inf
+        for b in range(q.shape[0]):
+            e, J, _ = exact_rows(t, q[b], kinds, radii, drop=term)
+            moved = 0.0
+            for got, (r, S) in ((e, ref[b][0]), (J, ref[b][1])):
+                u = S + EPS * np.abs(r[0]).max()
+                moved = max(moved, float(np.abs(np.array([float(x) for x in ek.flat(got)]) - r[0]).max() / (K_ROLL * u)))
+            least = min(least, moved)
+        out[term] = least
+    return out
+
+
+# ---- measured ratios (profiles/rolling_task_exact.json) -----------------------------------------------------------------------
+RATIOS = {}
+
+
+def note_ratios(who, name, re, rj, rz=None):
+    d = RATIOS.setdefault(who, {})
+    for key, v in (("e", re), ("J", rj), ("z", rz)):
+        if v is not None:
+            d[f"{name}_{key}"] = max(d.get(f"{name}_{key}", 0.0), float(v))
+
+
+def write_ratios():
+    """PINK_ROLLING_TASK_RATIOS=<file>: the worst ratios noted so far are merged into that JSON file, one block per
+    "host" / "reference" / "emu" / "gpu" (the host tests and the device tests of one session, and a later GPU session, add
+    theirs)."""
+    path = os.environ.get("PINK_ROLLING_TASK_RATIOS")
+    if not path or not RATIOS:
+        return
+    have = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            have = json.load(f)
+    for who, d in RATIOS.items():
+        have.setdefault(who, {}).update({n: float("%.3g" % v) for n, v in sorted(d.items())})
+    with open(path, "w") as f:
+        json.dump(have, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+# ---- the emulator behind BatchSolver.rolling_tasks --------------------------------------------------------------------------
+def with_rolling(api):
+    """The emulator behind BatchSolver's ``rolling_tasks`` (pinkhip_rolling_tasks_device's twin on host memory)."""
+    if hasattr(api, "rolling_tasks"):
+        return api
+    lib, vp, ll, ci = api.lib, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
+    lib.pinkhip_emu_rolling_tasks.argtypes = [vp, ll, vp, ci, vp, vp, vp, vp, ll, vp, ll, ci, vp]
+    lib.pinkhip_emu_last_error.restype = ctypes.c_char_p
+
+    def rolling_tasks(model, B, q, slots, kinds, radii, e, sE, J, sJ, row0, height_out=None):
+        n = len(slots)
+        s, k, r = (None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in ((slots, np.int32), (kinds, np.int32), (radii, np.float64)))
+        rc = lib.pinkhip_emu_rolling_tasks(model, B, q, n, *(None if a is None else a.ctypes.data for a in (s, k, r)), e, sE, J, sJ, int(row0), height_out)
+        if rc != 0:
+            raise PinkHipError(rc, lib.pinkhip_emu_last_error().decode())
+
+    api.rolling_tasks = rolling_tasks
+    return api
