@@ -82,9 +82,10 @@ int run_plan(const LaunchPlan &p, void *args) {
   return PINKHIP_OK;
 }
 
-// The kinematics kernels: one group of 8 / 32 / 64 lanes per robot, a lane per joint / tangent column (as pinkhip.hip)
-int run_fk(const pinkhip::ModelDev &m, long long B, pinkhip::LaneFn fn8, pinkhip::LaneFn fn32, pinkhip::LaneFn fn64, void *args) {
-  const int width = m.nv > m.nj ? m.nv : m.nj, per = width <= 8 ? 8 : width <= 32 ? 2 : 1;
+// The kinematics kernels: one group of `width` lanes per robot, the smallest of 8 / 32 / 64 that holds them (launch_grouped
+// of pinkhip.hip)
+int run_fk(int width, long long B, pinkhip::LaneFn fn8, pinkhip::LaneFn fn32, pinkhip::LaneFn fn64, void *args) {
+  const int per = width <= 8 ? 8 : width <= 32 ? 2 : 1;
   const pinkhip::LaneFn fn = width <= 8 ? fn8 : width <= 32 ? fn32 : fn64;
   for (long long b = 0; b < (B + per - 1) / per; ++b) pinkhip::emu_run_block(b, fn, args);
   return PINKHIP_OK;
@@ -159,7 +160,7 @@ int pinkhip_emu_model_destroy(void *m) {
 int pinkhip_emu_fk(void *mp, long long B, const double *q, double *T_frames, double *J_body) {
   EmuModel *m = static_cast<EmuModel *>(mp);
   pinkhip::FkArgs a{m->dev, B, q, T_frames, J_body};
-  return run_fk(m->dev, B, lane_main_fk<8>, lane_main_fk<32>, lane_main_fk<64>, &a);
+  return run_fk(pinkhip::fk_group_width(m->dev), B, lane_main_fk<8>, lane_main_fk<32>, lane_main_fk<64>, &a);
 }
 int pinkhip_emu_fk_frame_tasks(void *mp, long long B, const double *q, const double *T_target, double *T_frames,
                                double *e, long long sE, double *J, long long sJ) {
@@ -170,7 +171,7 @@ int pinkhip_emu_fk_frame_tasks(void *mp, long long B, const double *q, const dou
   a.J_out = J;
   a.sE = sE;
   a.sJo = sJ;
-  return run_fk(m->dev, B, lane_main_fk_fused<8>, lane_main_fk_fused<32>, lane_main_fk_fused<64>, &a);
+  return run_fk(pinkhip::fk_group_width(m->dev), B, lane_main_fk_fused<8>, lane_main_fk_fused<32>, lane_main_fk_fused<64>, &a);
 }
 // centre-of-mass rows, mirroring pinkhip_com_create / _com_destroy / _com_task_device on host memory
 int pinkhip_emu_com_create(void *mp, int nj, const double *mass, const double *com, void **out) {
@@ -208,7 +209,7 @@ int pinkhip_emu_com_task(void *mp, void *cp, long long B, const double *q, const
   pinkhip::ComArgs a{m->dev, c->dev, B, q, target, target_batched, e, J, sE, sJ, row0, com_out};
   if (const char *bad = pinkhip::com_task_fault(a)) return pinkhip::refuse(g_err, PINKHIP_E_INVALID, bad);
   if (B == 0) return PINKHIP_OK;
-  return run_fk(m->dev, B, lane_main_com<8>, lane_main_com<32>, lane_main_com<64>, &a);
+  return run_fk(pinkhip::fk_group_width(m->dev), B, lane_main_com<8>, lane_main_com<32>, lane_main_com<64>, &a);
 }
 // the ManipulabilityTask row, mirroring pinkhip_manipulability_task_device on host memory
 int pinkhip_emu_manipulability_task(void *mp, long long B, const double *q, int frame, int reference_frame, int row_mask, double rate,
@@ -220,7 +221,7 @@ int pinkhip_emu_manipulability_task(void *mp, long long B, const double *q, int 
   if (const char *bad = pinkhip::manip_path_fault(m->dev.nj, m->dev.parent, m->dev.jtype, m->dev.frame_joint[frame]))
     return pinkhip::refuse(g_err, PINKHIP_E_UNSUPPORTED, bad);
   if (B == 0) return PINKHIP_OK;
-  return run_fk(m->dev, B, lane_main_manip<8>, lane_main_manip<32>, lane_main_manip<64>, &a);
+  return run_fk(pinkhip::fk_group_width(m->dev), B, lane_main_manip<8>, lane_main_manip<32>, lane_main_manip<64>, &a);
 }
 // Test infrastructure: the path check on a tree given as its tables, without a device model in front of it (a model of more
 // than 64 joints cannot be created: nv <= PINKHIP_MAX_NV)
@@ -239,10 +240,7 @@ int pinkhip_emu_rolling_tasks(void *mp, long long B, const double *q, int n, con
   int code = PINKHIP_E_INVALID;
   if (const char *bad = pinkhip::rolling_task_fault(a, m->dev.frame_root_joint, code)) return pinkhip::refuse(g_err, code, bad);
   if (B == 0) return PINKHIP_OK;
-  const int width = pinkhip::rolling_group_width(m->dev.nj), per = pinkhip::kWave / width;
-  const pinkhip::LaneFn fn = width == 8 ? lane_main_rolling<8> : width == 32 ? lane_main_rolling<32> : lane_main_rolling<64>;
-  for (long long b = 0; b < (B + per - 1) / per; ++b) pinkhip::emu_run_block(b, fn, &a);
-  return PINKHIP_OK;
+  return run_fk(pinkhip::rolling_group_width(m->dev.nj), B, lane_main_rolling<8>, lane_main_rolling<32>, lane_main_rolling<64>, &a);
 }
 // Test infrastructure: the joint-count refusal on a bare count, without a device model in front of it (a model of more than
 // 64 joints cannot be created: nv <= PINKHIP_MAX_NV)
@@ -261,7 +259,7 @@ int pinkhip_emu_rolling_joint_check(int nj) {
 int pinkhip_emu_step(void *mp, long long B, const pinkhip_step *st) {
   EmuModel *m = static_cast<EmuModel *>(mp);
   pinkhip::FkArgs a = pinkhip::step_args(m->dev, B, *st);
-  return run_fk(m->dev, B, lane_main_step<8>, lane_main_step<32>, lane_main_step<64>, &a);
+  return run_fk(pinkhip::fk_group_width(m->dev), B, lane_main_step<8>, lane_main_step<32>, lane_main_step<64>, &a);
 }
 int pinkhip_emu_rollout_step(const pinkhip_desc *d, void *mp, const pinkhip_rollout_step *st) { return rollout_step(d, mp, st, nullptr); }
 int pinkhip_emu_rollout_step_warm(const pinkhip_desc *d, void *mp, const pinkhip_rollout_step *st, const pinkhip_warm *warm) {

@@ -290,6 +290,14 @@ inline int group_bcast_i(int v, int src) {
   if (src < 0 || src >= W) std::abort();
   return lane_shfl_i(v, (emu().cur & ~(W - 1)) | src);
 }
+template <int W>
+inline double uniform_bcast(double v, int src) {  // (wave.h: src uniform over the wave)
+  if constexpr (W == kWave) {
+    return bcast(v, src);
+  } else {
+    return group_bcast<W>(v, src);
+  }
+}
 // (wave.h: the two rows of 16 lanes of every 32-lane half exchange their values; a = the even row's, b = the odd row's)
 inline void row_pair(double v, double &a, double &b) {
   const int l = emu().cur;

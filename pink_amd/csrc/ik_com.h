@@ -48,9 +48,6 @@ struct ComArgs {
   double *com_out;  // [B, 3] or NULL
 };
 
-// LDS per instance: world poses of the joints [nj, 12] + ancestor pointers [nj]
-__device__ __host__ inline int com_lds_doubles(int nj) { return 12 * nj + ((nj + 1) & ~1); }
-
 // ---- host side: the tables of a model's masses, laid out in one buffer (shared by libpinkhip.so and the emulator) ----
 struct ComImage {
   std::vector<char> bytes;
@@ -137,37 +134,22 @@ inline const char *com_task_fault(const ComArgs &a) {
   return nullptr;
 }
 
-// Value of lane `src` of the group (src uniform over the wave): v_readlane for a whole wave, the LDS crossbar otherwise
-template <int W>
-__device__ __forceinline__ double com_bcast(double v, int src) {
-  if constexpr (W == kWave) {
-    return bcast(v, src);
-  } else {
-    return group_bcast<W>(v, src);
-  }
-}
-
 // The centre of mass of one instance and its Jacobian by a group of W lanes (W >= nj), the mapping of ik_fk_instance:
-//   1.-2. lane = joint: pose in the parent frame, pointer jumping to world poses (as ik_fk_instance);
+//   1.-2. lane = joint: pose in the parent frame, pointer jumping to world poses (compose_world_poses);
 //   3. lane = joint k: first moment m_k x_k, kept in registers;
 //   4. lane = tangent column j: nj broadcast steps sum the moments of the joints in the subtree of the column's joint
 //      (descendant bit mask) and of all joints; no LDS traffic in that loop;
 //   5. the column, stored by column lane: consecutive lanes write consecutive addresses of a row of J.
 template <int W>
 __device__ __forceinline__ void ik_com_instance(const ComArgs &a, long long block) {
-  constexpr int G = kWave / W;
   const ModelDev &m = a.m;
-  const int lane = lane_id();
-  const int g = lane / W, li = lane & (W - 1);
-  long long b = block * G + g;
-  const bool valid = b < a.B;
-  if (!valid) b = a.B - 1;
-  double *oM = shared_base() + (long long)g * com_lds_doubles(m.nj);
-  int *anc = reinterpret_cast<int *>(oM + 12 * m.nj);
+  const GroupLane gl = group_lane<W>(block, a.B, m.nj);
+  const int li = gl.li, jl = gl.jl;
+  const long long b = gl.b;
+  const bool valid = gl.valid, isj = gl.isj;
+  double *oM = shared_base() + (long long)gl.g * pose_lds_doubles(m.nj);
   const double *q = a.q + b * (long long)m.nq;
 
-  const bool isj = li < m.nj;
-  const int jl = isj ? li : 0;
   // The tables of this lane's joint and of its first tangent column are requested before the poses are composed (the
   // kernel is bound by dependent round trips, as ik_fk_instance is)
   const double mk = isj ? a.c.mass[jl] : 0.0;
@@ -180,43 +162,9 @@ __device__ __forceinline__ void ik_com_instance(const ComArgs &a, long long bloc
   const int ti = li < 3 ? li : 0;
   const double tgt = a.target[(a.target_batched ? 3 * b : 0) + ti];
 
-  // 1. pose of joint li in its parent's frame
-  double T[12];
-  {
-    double Tj[12];
-    joint_transform(m, jl, q + m.idx_q[jl], Tj);
-    se3_mul(m.placement + 12 * jl, Tj, T);
-  }
-  int up = isj ? m.parent[jl] : -1;
-  if (isj) {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) oM[12 * li + i] = T[i];
-    anc[li] = up;
-  }
-  wave_sync();
-  // 2. pointer jumping: T_j <- T_up(j) T_j, up(j) <- up(up(j)) until every joint is expressed in the world
-  while (wave_any(up >= 0)) {
-    double P[12];
-    int upup = -1;
-    if (up >= 0) {
-#pragma unroll
-      for (int i = 0; i < 12; ++i) P[i] = oM[12 * up + i];
-      upup = anc[up];
-    }
-    wave_sync();  // every lane has read the old poses and pointers
-    if (up >= 0) {
-      double N[12];
-      se3_mul(P, T, N);
-#pragma unroll
-      for (int i = 0; i < 12; ++i) {
-        T[i] = N[i];
-        oM[12 * li + i] = N[i];
-      }
-      anc[li] = upup;
-      up = upup;
-    }
-    wave_sync();
-  }
+  // 1.-2. world pose of joint li, in this lane's registers and (all joints) in oM
+  const Pose X = compose_world_poses(m, gl, joint_pose_in_parent(m, jl, q + m.idx_q[jl]), oM);
+  const double(&T)[12] = X.T;
   // 3. first moment of the mass attached to joint li (a lane without a joint, or a massless joint: exactly zero)
   double mx[3];
 #pragma unroll
@@ -240,7 +188,7 @@ __device__ __forceinline__ void ik_com_instance(const ComArgs &a, long long bloc
       const bool in = ((D >> k) & 1ull) != 0;
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        const double v = com_bcast<W>(mx[i], k);
+        const double v = uniform_bcast<W>(mx[i], k);
         ct[i] += v;
         s[i] += in ? v : 0.0;
       }

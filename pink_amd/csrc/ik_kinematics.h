@@ -123,6 +123,101 @@ __device__ inline void joint_transform(const ModelDev &m, int a, const double *q
   }
 }
 
+__device__ __forceinline__ void cross3(const double *a, const double *b, double *c) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// ---- The prologue of the row kernels (ik_com.h, ik_manip.h, ik_rolling.h): one robot per group of W lanes, lane = joint,
+// world poses of the joints by pointer jumping.  ik_fk_instance and ik_rolling_instance run the same algorithm on copies of
+// their own (see there).  Poses travel by value: the form whose register allocation stays closest to the loop written out
+// in place. ----
+struct Pose {
+  double T[12];  // rotation row-major, translation
+};
+
+// Which robot a lane works for and which of the robot's lanes it is.  A group past the end of the batch recomputes the last
+// robot (b = B - 1) and stores nothing (valid = false): every lane takes part in the group-wide steps.
+struct GroupLane {
+  int g, li;  // group inside the wavefront, lane inside the group
+  long long b;
+  bool valid;
+  bool isj;  // the lane has a joint: li < nj
+  int jl;    // that joint, or 0: an index every lane may load tables at
+};
+template <int W>
+__device__ __forceinline__ GroupLane group_lane(long long block, long long B, int nj) {
+  const int lane = lane_id();
+  GroupLane r{lane / W, lane & (W - 1), block * (kWave / W) + lane / W};
+  r.valid = r.b < B;
+  if (!r.valid) r.b = B - 1;
+  r.isj = r.li < nj;
+  r.jl = r.isj ? r.li : 0;
+  return r;
+}
+
+// LDS per instance: world poses of the joints [nj, 12] + ancestor pointers [nj]
+__device__ __host__ inline int pose_lds_doubles(int nj) { return 12 * nj + ((nj + 1) & ~1); }
+
+// pose of joint jl in its parent's frame; qj = the joint's own entries of q
+__device__ __forceinline__ Pose joint_pose_in_parent(const ModelDev &m, int jl, const double *qj) {
+  Pose X;
+  double Tj[12];
+  joint_transform(m, jl, qj, Tj);
+  se3_mul(m.placement + 12 * jl, Tj, X.T);
+  return X;
+}
+
+// Pointer jumping: T_j <- T_up(j) T_j, up(j) <- up(up(j)) until every joint is expressed in the world, ceil(log2(depth))
+// rounds.  X: the pose of the lane's joint in its parent's frame.  Returns its world pose; the world poses of all joints of
+// the group are in oM [nj, 12] (the ancestor pointers behind them) once every lane has returned.
+__device__ __forceinline__ Pose compose_world_poses(const ModelDev &m, const GroupLane &gl, Pose X, double *oM) {
+  const int li = gl.li;
+  int *anc = reinterpret_cast<int *>(oM + 12 * m.nj);
+  int up = gl.isj ? m.parent[gl.jl] : -1;
+  if (gl.isj) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) oM[12 * li + i] = X.T[i];
+    anc[li] = up;
+  }
+  wave_sync();
+  while (wave_any(up >= 0)) {
+    double P[12];
+    int upup = -1;
+    if (up >= 0) {
+#pragma unroll
+      for (int i = 0; i < 12; ++i) P[i] = oM[12 * up + i];
+      upup = anc[up];
+    }
+    wave_sync();  // every lane has read the old poses and pointers
+    if (up >= 0) {
+      double N[12];
+      se3_mul(P, X.T, N);
+#pragma unroll
+      for (int i = 0; i < 12; ++i) {
+        X.T[i] = N[i];
+        oM[12 * li + i] = N[i];
+      }
+      anc[li] = upup;
+      up = upup;
+    }
+    wave_sync();
+  }
+  return X;
+}
+
+// Pose of a frame slot in the world: its placement on joint `joint` (world pose in oM), or the placement itself on the
+// world (joint = -1)
+__device__ __forceinline__ void frame_pose_in_world(int joint, const double *placement, const double *oM, double *F) {
+  if (joint >= 0) {
+    se3_mul(oM + 12 * joint, placement, F);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) F[i] = placement[i];
+  }
+}
+
 // q_j <- q_j (+) v_j for one joint, in place (pink/configuration.py:273-293: pin.integrate)
 __device__ inline void integrate_joint(const ModelDev &m, int j, double *q, const double *v) {
   if (m.jtype[j] != JOINT_FREE_FLYER) {
@@ -253,6 +348,8 @@ struct FkArgs {
 // LDS per instance: oM [nj, 12] + inverse frame poses [nf, 12] + ancestor pointers [nj] + Jlog6 [nf, 36] + the
 // scalar configuration of every joint [nj] (whole-step kernel)
 __device__ __host__ inline int fk_lds_doubles(int nj, int nf) { return 12 * (nj + nf) + ((nj + 1) & ~1) + 36 * nf + ((nj + 1) & ~1); }
+// lanes per instance: one per joint / tangent column (the launch takes the smallest of 8 / 32 / 64 that holds them)
+inline int fk_group_width(const ModelDev &m) { return m.nv > m.nj ? m.nv : m.nj; }
 
 // Forward kinematics and body (LOCAL) frame Jacobians of one instance by a group of W lanes (W >= nj).
 //   1. lane = joint: local transform (sin / cos), pose in the parent frame;
@@ -360,7 +457,9 @@ __device__ __forceinline__ void ik_fk_instance(const FkArgs &a, long long block,
     anc[li] = up;
   }
   wave_sync();
-  // 2. pointer jumping: T_j <- T_up(j) T_j, up(j) <- up(up(j)) until every joint is expressed in the world
+  // 2. pointer jumping: T_j <- T_up(j) T_j, up(j) <- up(up(j)) until every joint is expressed in the world.
+  // compose_world_poses written out: calling it here moves the registers and the scratch of every kernel built from this
+  // function, the whole-step kernels among them.  The two must stay the same algorithm.
   while (wave_any(up >= 0)) {
     double P[12];
     int upup = -1;
@@ -547,94 +646,67 @@ __device__ __forceinline__ void ik_fk_instance(const FkArgs &a, long long block,
     }
     }
   } else {
-  // 3. frames
-  for (int f = li; f < m.nf; f += W) {
-    double F[12];
-    const int fj = m.frame_joint[f];
-    if (fj >= 0) {
-      se3_mul(oM + 12 * fj, m.frame_placement + 12 * f, F);
-    } else {
+    // 3. frames
+    for (int f = li; f < m.nf; f += W) {
+      double F[12];
+      const int fj = m.frame_joint[f];
+      if (fj >= 0) {
+        se3_mul(oM + 12 * fj, m.frame_placement + 12 * f, F);
+      } else {
 #pragma unroll
-      for (int i = 0; i < 12; ++i) F[i] = m.frame_placement[12 * f + i];
-    }
-    if (valid && a.T_frames) {
-#pragma unroll
-      for (int i = 0; i < 12; ++i) a.T_frames[(b * m.nf + f) * 12 + i] = F[i];
-    }
-    // inverse: (R^T, -R^T p)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) fMo[12 * f + 3 * i + j] = F[3 * j + i];
-      fMo[12 * f + 9 + i] = -(F[i] * F[9] + F[3 + i] * F[10] + F[6 + i] * F[11]);
-    }
-    if constexpr (FUSED) {
-      double Tt[12], R[9], pr[3], xi[6], Jl[36];
-#pragma unroll
-      for (int i = 0; i < 12; ++i) Tt[i] = a.T_target[b * (a.sTb ? a.sTb : 12LL * m.nf) + f * a.sTf + i];
-      se3_act_inv(F, Tt, R, pr);  // e = log6(T_frame^-1 T_target), frame_task.py:181-193
-      log6(R, pr, xi);
-      if (valid) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) a.e_out[b * a.sE + 6 * f + i] = xi[i];
+        for (int i = 0; i < 12; ++i) F[i] = m.frame_placement[12 * f + i];
       }
-      se3_act_inv(Tt, F, R, pr);  // J = -Jlog6(T_target^-1 T_frame) J_body, frame_task.py:222-227
-      jlog6(R, pr, Jl);
+      if (valid && a.T_frames) {
 #pragma unroll
-      for (int i = 0; i < 36; ++i) Jls[36 * f + i] = Jl[i];
-    }
-  }
-  wave_sync();
-  // 4. body Jacobians: lane = tangent column
-  for (int j = li; j < m.nv; j += W) {
-    const int jt = m.dof_joint[j], sub = m.dof_sub[j], ty = m.jtype[jt];
-    for (int f = 0; f < m.nf; ++f) {
-      double col[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      if (m.anc[f * m.nj + jt]) {
-        double X[12];
-        se3_mul(fMo + 12 * f, oM + 12 * jt, X);  // joint frame -> frame
-        double u[3];
-        if (ty == JOINT_FREE_FLYER) {
-          const int k = sub % 3;  // R[:, k], selected without indexing the register array dynamically (scratch)
-          u[0] = k == 0 ? X[0] : (k == 1 ? X[1] : X[2]);
-          u[1] = k == 0 ? X[3] : (k == 1 ? X[4] : X[5]);
-          u[2] = k == 0 ? X[6] : (k == 1 ? X[7] : X[8]);
-        } else {
-          const double *ax = m.axis + 3 * jt;
-#pragma unroll
-          for (int i = 0; i < 3; ++i) u[i] = X[3 * i] * ax[0] + X[3 * i + 1] * ax[1] + X[3 * i + 2] * ax[2];
-        }
-        const bool angular = (ty == JOINT_REVOLUTE) || (ty == JOINT_FREE_FLYER && sub >= 3);
-        if (angular) {  // [p x (R u); R u]
-          col[0] = X[10] * u[2] - X[11] * u[1];
-          col[1] = X[11] * u[0] - X[9] * u[2];
-          col[2] = X[9] * u[1] - X[10] * u[0];
-          col[3] = u[0];
-          col[4] = u[1];
-          col[5] = u[2];
-        } else {  // [R u; 0]
-          col[0] = u[0];
-          col[1] = u[1];
-          col[2] = u[2];
-        }
+        for (int i = 0; i < 12; ++i) a.T_frames[(b * m.nf + f) * 12 + i] = F[i];
       }
-      if (valid) {
-        if constexpr (FUSED) {
-          double *Jo = a.J_out + b * a.sJo + (long long)(6 * f) * m.nv;
-          const double *Jl = Jls + 36 * f;
+      // inverse: (R^T, -R^T p)
 #pragma unroll
-          for (int i = 0; i < 6; ++i) {
-            double sacc = 0.0;
+      for (int i = 0; i < 3; ++i) {
 #pragma unroll
-            for (int r = 0; r < 6; ++r) sacc -= Jl[6 * i + r] * col[r];
-            Jo[i * m.nv + j] = sacc;
+        for (int j = 0; j < 3; ++j) fMo[12 * f + 3 * i + j] = F[3 * j + i];
+        fMo[12 * f + 9 + i] = -(F[i] * F[9] + F[3 + i] * F[10] + F[6 + i] * F[11]);
+      }
+    }
+    wave_sync();
+    // 4. body Jacobians: lane = tangent column
+    for (int j = li; j < m.nv; j += W) {
+      const int jt = m.dof_joint[j], sub = m.dof_sub[j], ty = m.jtype[jt];
+      for (int f = 0; f < m.nf; ++f) {
+        double col[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (m.anc[f * m.nj + jt]) {
+          double X[12];
+          se3_mul(fMo + 12 * f, oM + 12 * jt, X);  // joint frame -> frame
+          double u[3];
+          if (ty == JOINT_FREE_FLYER) {
+            const int k = sub % 3;  // R[:, k], selected without indexing the register array dynamically (scratch)
+            u[0] = k == 0 ? X[0] : (k == 1 ? X[1] : X[2]);
+            u[1] = k == 0 ? X[3] : (k == 1 ? X[4] : X[5]);
+            u[2] = k == 0 ? X[6] : (k == 1 ? X[7] : X[8]);
+          } else {
+            const double *ax = m.axis + 3 * jt;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) u[i] = X[3 * i] * ax[0] + X[3 * i + 1] * ax[1] + X[3 * i + 2] * ax[2];
           }
-        } else {
+          const bool angular = (ty == JOINT_REVOLUTE) || (ty == JOINT_FREE_FLYER && sub >= 3);
+          if (angular) {  // [p x (R u); R u]
+            col[0] = X[10] * u[2] - X[11] * u[1];
+            col[1] = X[11] * u[0] - X[9] * u[2];
+            col[2] = X[9] * u[1] - X[10] * u[0];
+            col[3] = u[0];
+            col[4] = u[1];
+            col[5] = u[2];
+          } else {  // [R u; 0]
+            col[0] = u[0];
+            col[1] = u[1];
+            col[2] = u[2];
+          }
+        }
+        if (valid) {
 #pragma unroll
           for (int r = 0; r < 6; ++r) a.J_body[((b * m.nf + f) * 6 + r) * m.nv + j] = col[r];
         }
       }
-    }
     }
   }
 }

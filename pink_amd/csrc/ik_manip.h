@@ -18,7 +18,6 @@
 #include <cstdint>
 
 #include "../../include/pinkhip.h"
-#include "ik_com.h"
 #include "ik_kinematics.h"
 
 namespace pinkhip {
@@ -64,14 +63,8 @@ inline const char *manip_path_fault(int nj, const int *parent, const int *jtype,
   return nullptr;
 }
 
-__device__ __forceinline__ void manip_cross(const double *a, const double *b, double *c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 // One instance by a group of W lanes (W >= nj), the mapping of ik_com_instance:
-//   1.-2. lane = joint: pose in the parent frame, pointer jumping to world poses;
+//   1.-2. lane = joint: pose in the parent frame, pointer jumping to world poses (compose_world_poses);
 //   3. lane = joint k: its column (v, w) of the frame's Jacobian, zero off the path (cm: the kept rows of it);
 //   4. A = sum over the lanes of column column^T (21 group sums), L D L^T in every lane's registers, m from the pivots,
 //      P_k by two triangular solves on the lane's own column;
@@ -80,19 +73,14 @@ __device__ __forceinline__ void manip_cross(const double *a, const double *b, do
 //   6. the row, stored by joint lane.
 template <int W>
 __device__ __forceinline__ void ik_manip_instance(const ManipArgs &a, long long block) {
-  constexpr int G = kWave / W;
   const ModelDev &m = a.m;
-  const int lane = lane_id();
-  const int g = lane / W, li = lane & (W - 1);
-  long long b = block * G + g;
-  const bool valid = b < a.B;
-  if (!valid) b = a.B - 1;
-  double *oM = shared_base() + (long long)g * com_lds_doubles(m.nj);
-  int *anc = reinterpret_cast<int *>(oM + 12 * m.nj);
+  const GroupLane gl = group_lane<W>(block, a.B, m.nj);
+  const int li = gl.li, jl = gl.jl;
+  const long long b = gl.b;
+  const bool valid = gl.valid, isj = gl.isj;
+  double *oM = shared_base() + (long long)gl.g * pose_lds_doubles(m.nj);
   const double *q = a.q + b * (long long)m.nq;
 
-  const bool isj = li < m.nj;
-  const int jl = isj ? li : 0;
   // the tables of this lane's joint and of the frame, requested before the poses are composed
   const bool onpath = isj && m.anc[a.frame * m.nj + jl] != 0;
   const int my_col = m.idx_v[jl];
@@ -103,43 +91,9 @@ __device__ __forceinline__ void ik_manip_instance(const ManipArgs &a, long long 
 #pragma unroll
   for (int i = 0; i < 12; ++i) Fp[i] = m.frame_placement[12 * a.frame + i];
 
-  // 1. pose of joint li in its parent's frame
-  double T[12];
-  {
-    double Tj[12];
-    joint_transform(m, jl, q + m.idx_q[jl], Tj);
-    se3_mul(m.placement + 12 * jl, Tj, T);
-  }
-  int up = isj ? m.parent[jl] : -1;
-  if (isj) {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) oM[12 * li + i] = T[i];
-    anc[li] = up;
-  }
-  wave_sync();
-  // 2. pointer jumping: T_j <- T_up(j) T_j, up(j) <- up(up(j)) until every joint is expressed in the world
-  while (wave_any(up >= 0)) {
-    double P[12];
-    int upup = -1;
-    if (up >= 0) {
-#pragma unroll
-      for (int i = 0; i < 12; ++i) P[i] = oM[12 * up + i];
-      upup = anc[up];
-    }
-    wave_sync();  // every lane has read the old poses and pointers
-    if (up >= 0) {
-      double N[12];
-      se3_mul(P, T, N);
-#pragma unroll
-      for (int i = 0; i < 12; ++i) {
-        T[i] = N[i];
-        oM[12 * li + i] = N[i];
-      }
-      anc[li] = upup;
-      up = upup;
-    }
-    wave_sync();
-  }
+  // 1.-2. world pose of joint li, in this lane's registers and (all joints) in oM
+  const Pose X = compose_world_poses(m, gl, joint_pose_in_parent(m, jl, q + m.idx_q[jl]), oM);
+  const double(&T)[12] = X.T;
   // 3. the column of joint li: world axis u through p_k = T[9..11]
   double c[6];
   {
@@ -147,19 +101,14 @@ __device__ __forceinline__ void ik_manip_instance(const ManipArgs &a, long long 
                          T[6] * ax0 + T[7] * ax1 + T[8] * ax2};
     const double pk[3] = {T[9], T[10], T[11]};
     if (a.world) {  // spatial Jacobian: the twist at the world origin, (p_k x u, u)
-      manip_cross(pk, u, c);
+      cross3(pk, u, c);
       c[3] = u[0], c[4] = u[1], c[5] = u[2];
     } else {  // body Jacobian: R_f^T (u x (p_f - p_k)), R_f^T u
       double Tf[12];
-      if (fj >= 0) {
-        se3_mul(oM + 12 * fj, Fp, Tf);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) Tf[i] = Fp[i];
-      }
+      frame_pose_in_world(fj, Fp, oM, Tf);
       const double d[3] = {Tf[9] - pk[0], Tf[10] - pk[1], Tf[11] - pk[2]};
       double l[3];
-      manip_cross(u, d, l);
+      cross3(u, d, l);
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         c[i] = Tf[i] * l[0] + Tf[3 + i] * l[1] + Tf[6 + i] * l[2];
@@ -233,8 +182,8 @@ __device__ __forceinline__ void ik_manip_instance(const ManipArgs &a, long long 
     double Pk[6], ck[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-      Pk[i] = com_bcast<W>(Pc[i], k);
-      ck[i] = com_bcast<W>(c[i], k);
+      Pk[i] = uniform_bcast<W>(Pc[i], k);
+      ck[i] = uniform_bcast<W>(c[i], k);
     }
     // (lane index = joint index, and build_model_image (model_tables.h) refuses a model whose parents do not come before
     // their children: along a path joint order, lane order and column order are one)
@@ -243,8 +192,8 @@ __device__ __forceinline__ void ik_manip_instance(const ManipArgs &a, long long 
     const double wa[3] = {le ? c[3] : ck[3], le ? c[4] : ck[4], le ? c[5] : ck[5]};
     const double vb[3] = {le ? ck[0] : c[0], le ? ck[1] : c[1], le ? ck[2] : c[2]};
     double hl[3], ha[3];
-    manip_cross(wa, vb, hl);
-    manip_cross(c + 3, ck + 3, ha);
+    cross3(wa, vb, hl);
+    cross3(c + 3, ck + 3, ha);
     const double lin = Pk[0] * hl[0] + Pk[1] * hl[1] + Pk[2] * hl[2];
     const double ang = Pk[3] * ha[0] + Pk[4] * ha[1] + Pk[5] * ha[2];
     acc += lin + (le ? ang : 0.0);

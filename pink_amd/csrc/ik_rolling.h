@@ -23,7 +23,6 @@
 #include <cstdint>
 
 #include "../../include/pinkhip.h"
-#include "ik_com.h"
 #include "ik_kinematics.h"
 
 namespace pinkhip {
@@ -96,32 +95,21 @@ inline const char *rolling_task_fault(const RollingArgs &a, const int *root_join
 // tangent dimension does not widen the group)
 inline int rolling_group_width(int nj) { return nj <= 8 ? 8 : nj <= 32 ? 32 : 64; }
 
-__device__ __forceinline__ void rolling_cross(const double *a, const double *b, double *c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 // The rows of every wheel of one instance by a group of W lanes (W >= nj), the mapping of ik_manip_instance:
-//   1.-2. lane = joint: pose in the parent frame, pointer jumping to world poses (as ik_com_instance);
+//   1.-2. lane = joint: pose in the parent frame, pointer jumping to world poses (as compose_world_poses);
 //   3. per wheel (a loop uniform over the wavefront): hub and floor pose from the LDS poses, the contact point, the lane's
 //      own column(s) rotated into the floor's axes and stored by the joint lane; lane 0 stores e and the height.
 // Every tangent column belongs to exactly one joint lane: the rows are written completely, zeros included.
 template <int W>
 __device__ __forceinline__ void ik_rolling_instance(const RollingArgs &a, long long block) {
-  constexpr int G = kWave / W;
   const ModelDev &m = a.m;
-  const int lane = lane_id();
-  const int g = lane / W, li = lane & (W - 1);
-  long long b = block * G + g;
-  const bool valid = b < a.B;
-  if (!valid) b = a.B - 1;
-  double *oM = shared_base() + (long long)g * com_lds_doubles(m.nj);
-  int *anc = reinterpret_cast<int *>(oM + 12 * m.nj);
+  const GroupLane gl = group_lane<W>(block, a.B, m.nj);
+  const int li = gl.li, jl = gl.jl;
+  const long long b = gl.b;
+  const bool valid = gl.valid, isj = gl.isj;
+  double *oM = shared_base() + (long long)gl.g * pose_lds_doubles(m.nj);
   const double *q = a.q + b * (long long)m.nq;
 
-  const bool isj = li < m.nj;
-  const int jl = isj ? li : 0;
   // the tables of this lane's joint, requested before the poses are composed
   const int my_col = m.idx_v[jl];
   const int my_type = m.jtype[jl];
@@ -134,6 +122,7 @@ __device__ __forceinline__ void ik_rolling_instance(const RollingArgs &a, long l
     joint_transform(m, jl, q + m.idx_q[jl], Tj);
     se3_mul(m.placement + 12 * jl, Tj, T);
   }
+  int *anc = reinterpret_cast<int *>(oM + 12 * m.nj);
   int up = isj ? m.parent[jl] : -1;
   if (isj) {
 #pragma unroll
@@ -141,7 +130,10 @@ __device__ __forceinline__ void ik_rolling_instance(const RollingArgs &a, long l
     anc[li] = up;
   }
   wave_sync();
-  // 2. pointer jumping: T_j <- T_up(j) T_j, up(j) <- up(up(j)) until every joint is expressed in the world
+  // 2. pointer jumping: T_j <- T_up(j) T_j, up(j) <- up(up(j)) until every joint is expressed in the world.
+  // compose_world_poses (ik_kinematics.h) written out: with the pose returned by value the compiler fuses the other product
+  // of some sums a b + c d of the wheel loop below, and the rows come out a rounding apart; with the pose behind a pointer
+  // the kernel is 1 - 3 % slower.  The two must stay the same algorithm.
   while (wave_any(up >= 0)) {
     double P[12];
     int upup = -1;
@@ -178,18 +170,8 @@ __device__ __forceinline__ void ik_rolling_instance(const RollingArgs &a, long l
     const int fj = m.frame_joint[f], rj = m.frame_root_joint[f];
     const bool onpath = isj && m.anc[f * m.nj + jl] != 0;
     double TH[12], TF[12];  // hub and floor in the world (joint -1: the world itself)
-    if (fj >= 0) {
-      se3_mul(oM + 12 * fj, m.frame_placement + 12 * f, TH);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 12; ++i) TH[i] = m.frame_placement[12 * f + i];
-    }
-    if (rj >= 0) {
-      se3_mul(oM + 12 * rj, m.frame_root_placement + 12 * f, TF);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 12; ++i) TF[i] = m.frame_root_placement[12 * f + i];
-    }
+    frame_pose_in_world(fj, m.frame_placement + 12 * f, oM, TH);
+    frame_pose_in_world(rj, m.frame_root_placement + 12 * f, oM, TF);
     // floor normal n = R_F e_z, height z = n . (p_H - p_F), contact point p_C = p_H - rho n; d = p_C - p_k
     const double n0 = TF[2], n1 = TF[5], n2 = TF[8];
     const double z = n0 * (TH[9] - TF[9]) + n1 * (TH[10] - TF[10]) + n2 * (TH[11] - TF[11]);
@@ -205,7 +187,7 @@ __device__ __forceinline__ void ik_rolling_instance(const RollingArgs &a, long l
           const double s[3] = {ff ? T[k] : u[0], ff ? T[3 + k] : u[1], ff ? T[6 + k] : u[2]};
           const bool angular = ff ? c >= 3 : my_type == JOINT_REVOLUTE;
           double l[3];
-          rolling_cross(s, d, l);
+          cross3(s, d, l);
 #pragma unroll
           for (int i = 0; i < 3; ++i) l[i] = angular ? l[i] : s[i];
           double o[3];

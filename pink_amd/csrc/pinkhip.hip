@@ -246,6 +246,17 @@ int upload(pinkhip_handle *h, const pinkhip_desc *d, const pinkhip_problem *in, 
   return PINKHIP_OK;
 }
 
+// The kinematics kernels: one robot per group of `width` lanes -- the smallest of 8 / 32 / 64 that holds them -- 64 / width
+// robots per one-wavefront block, `per` doubles of LDS per robot
+#define PH_WIDTHS(kernel) pinkhip::kernel<8>, pinkhip::kernel<32>, pinkhip::kernel<64>
+template <class Args>
+void launch_grouped(hipStream_t stream, int width, int per, long long B, void (*k8)(Args), void (*k32)(Args), void (*k64)(Args),
+                           const Args &a) {
+  const int G = width <= 8 ? 8 : width <= 32 ? 2 : 1;
+  hipLaunchKernelGGL(width <= 8 ? k8 : width <= 32 ? k32 : k64, dim3((unsigned)((B + G - 1) / G)), dim3(pinkhip::kWave), 8 * G * per + 16,
+                     stream, a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -633,16 +644,7 @@ int pinkhip_fk_device(pinkhip_handle *h, const pinkhip_model *m, int64_t B, cons
   if (!q || (m->dev.nf > 0 && (!T_frames || !J_body))) return fail(h, PINKHIP_E_INVALID, "null pointer");
   PH_HIP(h, hipSetDevice(h->device));
   pinkhip::FkArgs a{m->dev, B, q, T_frames, J_body};
-  const int per = pinkhip::fk_lds_doubles(m->dev.nj, m->dev.nf);
-  const dim3 block(pinkhip::kWave);
-  const int width = m->dev.nv > m->dev.nj ? m->dev.nv : m->dev.nj;  // lanes per instance: one per joint / column
-  if (width <= 8) {
-    hipLaunchKernelGGL(pinkhip::ik_fk_kernel<8>, dim3((unsigned)((B + 7) / 8)), block, 8 * 8 * per + 16, h->stream, a);
-  } else if (width <= 32) {
-    hipLaunchKernelGGL(pinkhip::ik_fk_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
-  } else {
-    hipLaunchKernelGGL(pinkhip::ik_fk_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
-  }
+  launch_grouped(h->stream, pinkhip::fk_group_width(m->dev), pinkhip::fk_lds_doubles(m->dev.nj, m->dev.nf), B, PH_WIDTHS(ik_fk_kernel), a);
   PH_HIP(h, hipGetLastError());
   return PINKHIP_OK;
 }
@@ -662,16 +664,7 @@ int pinkhip_fk_frame_tasks_device(pinkhip_handle *h, const pinkhip_model *m, int
   a.J_out = J;
   a.sE = sE;
   a.sJo = sJ;
-  const int per = pinkhip::fk_lds_doubles(m->dev.nj, m->dev.nf);
-  const dim3 block(pinkhip::kWave);
-  const int width = m->dev.nv > m->dev.nj ? m->dev.nv : m->dev.nj;
-  if (width <= 8) {
-    hipLaunchKernelGGL(pinkhip::ik_fk_frame_tasks_kernel<8>, dim3((unsigned)((B + 7) / 8)), block, 8 * 8 * per + 16, h->stream, a);
-  } else if (width <= 32) {
-    hipLaunchKernelGGL(pinkhip::ik_fk_frame_tasks_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
-  } else {
-    hipLaunchKernelGGL(pinkhip::ik_fk_frame_tasks_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
-  }
+  launch_grouped(h->stream, pinkhip::fk_group_width(m->dev), pinkhip::fk_lds_doubles(m->dev.nj, m->dev.nf), B, PH_WIDTHS(ik_fk_frame_tasks_kernel), a);
   PH_HIP(h, hipGetLastError());
   return PINKHIP_OK;
 }
@@ -722,16 +715,7 @@ int pinkhip_com_task_device(pinkhip_handle *h, const pinkhip_model *m, const pin
   if (const char *bad = pinkhip::com_task_fault(a)) return fail(h, PINKHIP_E_INVALID, bad);
   if (B == 0) return PINKHIP_OK;
   PH_HIP(h, hipSetDevice(h->device));
-  const int per = pinkhip::com_lds_doubles(m->dev.nj);
-  const dim3 block(pinkhip::kWave);
-  const int width = m->dev.nv > m->dev.nj ? m->dev.nv : m->dev.nj;  // lanes per instance: one per joint / column
-  if (width <= 8) {
-    hipLaunchKernelGGL(pinkhip::ik_com_task_kernel<8>, dim3((unsigned)((B + 7) / 8)), block, 8 * 8 * per + 16, h->stream, a);
-  } else if (width <= 32) {
-    hipLaunchKernelGGL(pinkhip::ik_com_task_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
-  } else {
-    hipLaunchKernelGGL(pinkhip::ik_com_task_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
-  }
+  launch_grouped(h->stream, pinkhip::fk_group_width(m->dev), pinkhip::pose_lds_doubles(m->dev.nj), B, PH_WIDTHS(ik_com_task_kernel), a);
   PH_HIP(h, hipGetLastError());
   return PINKHIP_OK;
 }
@@ -753,16 +737,7 @@ int pinkhip_manipulability_task_device(pinkhip_handle *h, const pinkhip_model *m
   }
   if (B == 0) return PINKHIP_OK;
   PH_HIP(h, hipSetDevice(h->device));
-  const int per = pinkhip::com_lds_doubles(m->dev.nj);
-  const dim3 block(pinkhip::kWave);
-  const int width = m->dev.nv > m->dev.nj ? m->dev.nv : m->dev.nj;  // (the group width of the other row kernels of this model)
-  if (width <= 8) {
-    hipLaunchKernelGGL(pinkhip::ik_manipulability_task_kernel<8>, dim3((unsigned)((B + 7) / 8)), block, 8 * 8 * per + 16, h->stream, a);
-  } else if (width <= 32) {
-    hipLaunchKernelGGL(pinkhip::ik_manipulability_task_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
-  } else {
-    hipLaunchKernelGGL(pinkhip::ik_manipulability_task_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
-  }
+  launch_grouped(h->stream, pinkhip::fk_group_width(m->dev), pinkhip::pose_lds_doubles(m->dev.nj), B, PH_WIDTHS(ik_manipulability_task_kernel), a);
   PH_HIP(h, hipGetLastError());
   return PINKHIP_OK;
 }
@@ -778,16 +753,7 @@ int pinkhip_rolling_tasks_device(pinkhip_handle *h, const pinkhip_model *m, int6
   if (const char *bad = pinkhip::rolling_task_fault(a, root_joint, code)) return fail(h, code, bad);
   if (B == 0) return PINKHIP_OK;
   PH_HIP(h, hipSetDevice(h->device));
-  const int per = pinkhip::com_lds_doubles(m->dev.nj);
-  const dim3 block(pinkhip::kWave);
-  const int width = pinkhip::rolling_group_width(m->dev.nj);  // (lane = joint only: nv does not widen the group)
-  if (width == 8) {
-    hipLaunchKernelGGL(pinkhip::ik_rolling_tasks_kernel<8>, dim3((unsigned)((B + 7) / 8)), block, 8 * 8 * per + 16, h->stream, a);
-  } else if (width == 32) {
-    hipLaunchKernelGGL(pinkhip::ik_rolling_tasks_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
-  } else {
-    hipLaunchKernelGGL(pinkhip::ik_rolling_tasks_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
-  }
+  launch_grouped(h->stream, pinkhip::rolling_group_width(m->dev.nj), pinkhip::pose_lds_doubles(m->dev.nj), B, PH_WIDTHS(ik_rolling_tasks_kernel), a);
   PH_HIP(h, hipGetLastError());
   return PINKHIP_OK;
 }
@@ -806,16 +772,7 @@ int pinkhip_step_device(pinkhip_handle *h, const pinkhip_model *m, int64_t B, co
   if (st->step < 0 || st->step >= (1 << 23)) return fail(h, PINKHIP_E_INVALID, "bad step");
   PH_HIP(h, hipSetDevice(h->device));
   const pinkhip::FkArgs a = pinkhip::step_args(m->dev, B, *st);
-  const int per = pinkhip::fk_lds_doubles(m->dev.nj, m->dev.nf);
-  const dim3 block(pinkhip::kWave);
-  const int width = m->dev.nv > m->dev.nj ? m->dev.nv : m->dev.nj;
-  if (width <= 8) {
-    hipLaunchKernelGGL(pinkhip::ik_step_kernel<8>, dim3((unsigned)((B + 7) / 8)), block, 8 * 8 * per + 16, h->stream, a);
-  } else if (width <= 32) {
-    hipLaunchKernelGGL(pinkhip::ik_step_kernel<32>, dim3((unsigned)((B + 1) / 2)), block, 8 * 2 * per + 16, h->stream, a);
-  } else {
-    hipLaunchKernelGGL(pinkhip::ik_step_kernel<64>, dim3((unsigned)B), block, 8 * per + 16, h->stream, a);
-  }
+  launch_grouped(h->stream, pinkhip::fk_group_width(m->dev), pinkhip::fk_lds_doubles(m->dev.nj, m->dev.nf), B, PH_WIDTHS(ik_step_kernel), a);
   PH_HIP(h, hipGetLastError());
   return PINKHIP_OK;
 }

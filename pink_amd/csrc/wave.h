@@ -408,6 +408,15 @@ template <int W>
 __device__ __forceinline__ int group_bcast_i(int v, int src) {
   return lane_shfl_i(v, (lane_id() & ~(W - 1)) | src);
 }
+// Value of lane `src` of the group, src uniform over the wave: v_readlane for a whole wave, the LDS crossbar otherwise
+template <int W>
+__device__ __forceinline__ double uniform_bcast(double v, int src) {
+  if constexpr (W == kWave) {
+    return bcast(v, src);
+  } else {
+    return group_bcast<W>(v, src);
+  }
+}
 // The two rows of 16 lanes of every 32-lane half exchange their values on the VALU (gfx950
 // v_permlane16_swap_b32, no LDS-crossbar round trip): a and b hold, in both rows, the value of the
 // even and of the odd row.

@@ -145,45 +145,38 @@ class HybridState:
             self.com_key = key
         return self.dcom
 
+    def _frames_model(self, p: str, frames) -> int:
+        """Device model whose frame slots are ``frames``, behind the attributes ``<p>frames`` / ``<p>arrays`` / ``<p>model``;
+        built anew when the frames change."""
+        frames = tuple(frames)
+        if getattr(self, p + "frames") != frames:
+            from .rollout import ModelArrays
+
+            self._destroy_frames_model(p)
+            arrays = ModelArrays(self.model, list(frames))
+            setattr(self, p + "arrays", arrays)  # (kept: the descriptor points into its arrays)
+            setattr(self, p + "model", self.api.model_create(arrays.desc))
+            setattr(self, p + "frames", frames)
+        return getattr(self, p + "model")
+
+    def _destroy_frames_model(self, p: str) -> None:
+        if getattr(self, p + "model") is not None:
+            self.api.model_destroy(getattr(self, p + "model"))
+            setattr(self, p + "model", None)
+            setattr(self, p + "frames", None)
+
     def manipulability_model(self, frames) -> int:
         """Device model whose frame slots are the frames of the ManipulabilityTask slots (the frame-task model's slots each
         own six rows of the frame kernel)."""
-        frames = tuple(frames)
-        if self.mframes != frames:
-            from .rollout import ModelArrays
-
-            if self.mmodel is not None:
-                self.api.model_destroy(self.mmodel)
-            self.marrays = ModelArrays(self.model, list(frames))
-            self.mmodel = self.api.model_create(self.marrays.desc)
-            self.mframes = frames
-        return self.mmodel
+        return self._frames_model("m", frames)
 
     def rolling_model(self, frames) -> int:
         """Device model whose slots are the ``(hub, floor)`` pairs of the RollingTask / OmniwheelTask slots: relative slots,
         frame = hub, root = floor."""
-        frames = tuple(frames)
-        if self.rframes != frames:
-            from .rollout import ModelArrays
-
-            if self.rmodel is not None:
-                self.api.model_destroy(self.rmodel)
-            self.rarrays = ModelArrays(self.model, list(frames))
-            self.rmodel = self.api.model_create(self.rarrays.desc)
-            self.rframes = frames
-        return self.rmodel
+        return self._frames_model("r", frames)
 
     def constraint_model(self, frames) -> int:
-        frames = tuple(frames)
-        if self.cframes != frames:
-            from .rollout import ModelArrays
-
-            if self.cmodel is not None:
-                self.api.model_destroy(self.cmodel)
-            self.carrays = ModelArrays(self.model, list(frames))
-            self.cmodel = self.api.model_create(self.carrays.desc)
-            self.cframes = frames
-        return self.cmodel
+        return self._frames_model("c", frames)
 
     def buf(self, name: str, nbytes: int) -> int:
         have = self.bufs.get(name)
@@ -198,18 +191,12 @@ class HybridState:
         for ptr, _ in self.bufs.values():
             self.api.release(ptr)
         self.bufs = {}
-        if self.cmodel is not None:
-            self.api.model_destroy(self.cmodel)
-            self.cmodel = None
+        self._destroy_frames_model("c")
         if self.dcom is not None:
             self.api.com_destroy(self.dcom)
             self.dcom = None
-        if self.mmodel is not None:
-            self.api.model_destroy(self.mmodel)
-            self.mmodel = None
-        if self.rmodel is not None:
-            self.api.model_destroy(self.rmodel)
-            self.rmodel = None
+        self._destroy_frames_model("m")
+        self._destroy_frames_model("r")
         self.api.model_destroy(self.dmodel)
 
 

@@ -6,10 +6,11 @@ test_com_task_routes.py): computed once per session, shared by all three.
           joint 8 holds 80 % of the mass; no centre lies on its joint's axis
   tree34  the same generator, 33 joints behind a free-flyer (nj = 34, nv = 39)
   pend    tests/golden/double_pendulum.urdf through load_urdf
+  chain8, chain32  serial revolute chains of 8 and 32 joints, every joint with a mass: the deepest tree a group of 8 / 32 lanes
+          admits (3 and 5 rounds of pointer jumping), no idle lane in the group (nj = W), and a partial last wavefront
+          (B = 9: eight robots in one, the ninth alone in a second; B = 3 at two robots per wavefront)
 """
-import ctypes
 import functools
-import json
 import os
 
 import mpmath as mp
@@ -17,13 +18,12 @@ import numpy as np
 
 from oracle import exact_kinematics as ek
 from pink_amd import build_chain, load_urdf
-from pink_amd._lib import PinkHipError
 from pink_amd.configuration import Model
 from pink_amd.lie import SE3, exp3
 from pink_amd.rollout import ModelArrays
+from tests.row_kernel_kit import EPS, RatioRecorder, _split, random_configurations, ratio, with_com  # noqa: F401 (re-exported)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EPS = 2.0 ** -52
 K_COM = 8.0  # the bar tests/test_kinematics_exact.py holds poses and body Jacobians to
 H_FD = 1e-25
 
@@ -61,6 +61,17 @@ def tree(n, free_flyer, seed):
     return m
 
 
+def chain(n, seed):
+    """A serial chain of n revolute joints with random axes and placements, every joint with a mass off its axis."""
+    rng = np.random.default_rng(seed)
+    m = Model()
+    parent = -1
+    for i in range(n):
+        parent = m.add_joint(f"joint_{i + 1}", "revolute", parent, SE3(exp3(0.7 * rng.normal(size=3)), 0.3 * rng.normal(size=3)),
+                             rng.normal(size=3), -3.0, 3.0, 2.0, mass=float(rng.uniform(0.5, 5.0)), com=0.1 * rng.normal(size=3))
+    return m
+
+
 @functools.lru_cache(maxsize=None)
 def models():
     return {
@@ -68,29 +79,19 @@ def models():
         "tree12": (tree(12, False, 12), ["hand", "foot"]),
         "tree34": (tree(33, True, 12), ["hand", "foot"]),
         "pend": (load_urdf(os.path.join(ROOT, "tests", "golden", "double_pendulum.urdf")), []),
+        "chain8": (chain(8, 8), []),
+        "chain32": (chain(32, 32), []),
     }
 
 
-BATCH = {"arm6": 11, "tree12": 3, "tree34": 2, "pend": 3}
+BATCH = {"arm6": 11, "tree12": 3, "tree34": 2, "pend": 3, "chain8": 9, "chain32": 3}
 
 
 def configurations(name, B=None, seed=7):
     """Revolute angles over a few turns, prismatic coordinates in +-0.5, free-flyer quaternions with w < 0."""
     model = models()[name][0]
     B = BATCH[name] if B is None else B
-    rng = np.random.default_rng(seed + len(name))
-    q = np.zeros((B, model.nq))
-    for j in model.joints:
-        if j.kind == "free_flyer":
-            q[:, j.idx_q:j.idx_q + 3] = rng.normal(size=(B, 3))
-            qu = rng.normal(size=(B, 4))
-            qu[:, 3] = -np.abs(qu[:, 3]) - 0.1
-            q[:, j.idx_q + 3:j.idx_q + 7] = qu / np.linalg.norm(qu, axis=1, keepdims=True)
-        elif j.kind == "prismatic":
-            q[:, j.idx_q] = rng.uniform(-0.5, 0.5, size=B)
-        else:
-            q[:, j.idx_q] = rng.uniform(-6.0, 6.0, size=B)
-    return q
+    return random_configurations(model, B, np.random.default_rng(seed + len(name)))
 
 
 # ---- the 60-digit reference ---------------------------------------------------------------------------------------------
@@ -165,21 +166,6 @@ def exact_com_and_jacobian(t, q, mass, com):
     return c, J
 
 
-def _split(ref):
-    fl = ek.flat(ref)
-    hi = np.array([float(x) for x in fl])
-    with mp.workdps(ek.DPS):
-        lo = np.array([float(x - mp.mpf(h)) for x, h in zip(fl, hi)])
-    return hi, lo
-
-
-def ratio(dev, ref, S):
-    """Error in units of u = S + eps max|reference| (tests/test_kinematics_exact.py)."""
-    hi, lo = ref
-    u = S + EPS * np.abs(hi).max()
-    return float(np.abs((np.asarray(dev, dtype=np.float64).ravel() - hi) - lo).max() / u)
-
-
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """q and, per instance, (com (hi, lo), S_com, J (hi, lo), S_J): S is how far the exact result moves when every
@@ -204,59 +190,6 @@ def worst(name, c, J):
             max(ratio(J[b], ref[b][2], ref[b][3]) for b in range(q.shape[0])))
 
 
-# ---- measured ratios (profiles/com_task_exact.json) ---------------------------------------------------------------------------
-RATIOS = {}
-
-
-def note_ratios(who, name, rc, rj):
-    d = RATIOS.setdefault(who, {})
-    d[name + "_com"], d[name + "_J"] = max(d.get(name + "_com", 0.0), float(rc)), max(d.get(name + "_J", 0.0), float(rj))
-
-
-def write_ratios():
-    """PINK_COM_TASK_RATIOS=<file>: the worst ratios noted so far are merged into that JSON file, one block per
-    "host" / "emu" / "gpu" (the host tests and the device tests of one session, and a later GPU session, add theirs)."""
-    path = os.environ.get("PINK_COM_TASK_RATIOS")
-    if not path or not RATIOS:
-        return
-    have = {}
-    if os.path.exists(path):
-        with open(path) as f:
-            have = json.load(f)
-    for who, d in RATIOS.items():
-        have[who] = {n: float("%.3g" % v) for n, v in sorted(d.items())}
-    with open(path, "w") as f:
-        json.dump(have, f, indent=1, sort_keys=True)
-        f.write("\n")
-
-
-# ---- the emulator behind BatchSolver's centre-of-mass methods -----------------------------------------------------------------
-def with_com(api):
-    """The emulator behind the three centre-of-mass methods of BatchSolver (com_create / com_destroy / com_task)."""
-    if hasattr(api, "com_task"):
-        return api
-    lib, vp, ll, ci = api.lib, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
-    lib.pinkhip_emu_com_create.argtypes = [vp, ci, vp, vp, ctypes.POINTER(vp)]
-    lib.pinkhip_emu_com_destroy.argtypes = [vp]
-    lib.pinkhip_emu_com_task.argtypes = [vp, vp, ll, vp, vp, ci, vp, ll, vp, ll, ci, vp]
-    lib.pinkhip_emu_last_error.restype = ctypes.c_char_p
-
-    def check(rc):
-        if rc != 0:
-            raise PinkHipError(rc, lib.pinkhip_emu_last_error().decode())
-
-    def com_create(model, mass, com):
-        mass = np.ascontiguousarray(mass, dtype=np.float64)
-        com = np.ascontiguousarray(com, dtype=np.float64)
-        if mass.ndim != 1 or com.shape != (mass.shape[0], 3):
-            raise ValueError(f"mass [nj] and com [nj, 3] expected, got {mass.shape} and {com.shape}")
-        c = vp()
-        check(lib.pinkhip_emu_com_create(model, mass.shape[0], mass.ctypes.data, com.ctypes.data, ctypes.byref(c)))
-        return c.value
-
-    def com_task(model, com, B, q, target, target_batched, e, sE, J, sJ, row0, com_out=None):
-        check(lib.pinkhip_emu_com_task(model, com, B, q, target, int(bool(target_batched)), e, sE, J, sJ, int(row0), com_out))
-
-    api.com_create, api.com_task = com_create, com_task
-    api.com_destroy = lambda c: lib.pinkhip_emu_com_destroy(vp(c))
-    return api
+# ---- measured ratios: PINK_COM_TASK_RATIOS=<file> (profiles/com_task_exact.json) -------------------------------------------------
+_RECORDER = RatioRecorder("PINK_COM_TASK_RATIOS", "profiles/com_task_exact.json", ("com", "J"))
+RATIOS, note_ratios, write_ratios = _RECORDER.noted, _RECORDER.note, _RECORDER.write

@@ -13,9 +13,7 @@ A case is (model, frame, reference frame, mask); its configurations are drawn wi
 (regular) or 1e6 <= cond_2(A) <= 1e9 (the ill-conditioned band of arm6) -- the filter runs BEFORE anything is compared,
 and every configuration it keeps is tested.
 """
-import ctypes
 import functools
-import json
 import os
 
 import mpmath as mp
@@ -23,14 +21,14 @@ import numpy as np
 
 from oracle import exact_kinematics as ek
 from pink_amd import ReferenceFrame, build_chain
-from pink_amd._lib import PinkHipError
 from pink_amd.configuration import Model
 from pink_amd.kinematics_batch import BatchKinematics
 from pink_amd.lie import SE3, exp3
 from pink_amd.rollout import ModelArrays
+from tests.row_kernel_kit import EPS, RatioRecorder, _split, ratio, with_manipulability  # noqa: F401 (re-exported)
+from tests.row_kernel_kit import cross as _cross
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EPS = 2.0 ** -52
 K_UNITS = 8.0  # the project's bar (tests/test_kinematics_exact.py, tests/com_task_cases.py)
 LOCAL, WORLD = ReferenceFrame.LOCAL, ReferenceFrame.WORLD
 CUSTOM = np.array([1.0, 0.0, 1.0, 0.0, 1.0, 1.0])
@@ -162,10 +160,6 @@ def _adjoint_mp(T):
     return [R[i] + pxR[i] for i in range(3)] + [[z, z, z] + R[i] for i in range(3)]
 
 
-def _cross(a, b):
-    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
-
-
 @ek.precise
 def exact_rows(t, q, f, rf, rows):
     """(m, Jm [nv]) as mpf by the reference's own formula -- m sqrt(det A), Jm[i] = m vec(J H_i^T) . vec(A^-1) with the
@@ -202,21 +196,6 @@ def exact_rows(t, q, f, rf, rows):
     return [m], out
 
 
-def _split(ref):
-    fl = ek.flat(ref)
-    hi = np.array([float(x) for x in fl])
-    with mp.workdps(ek.DPS):
-        lo = np.array([float(x - mp.mpf(h)) for x, h in zip(fl, hi)])
-    return hi, lo
-
-
-def ratio(dev, ref, S):
-    """Error in units of u = S + eps max|reference| (tests/com_task_cases.py)."""
-    hi, lo = ref
-    u = S + EPS * np.abs(hi).max()
-    return float(np.abs((np.asarray(dev, dtype=np.float64).ravel() - hi) - lo).max() / u)
-
-
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """Per configuration of the case: (m (hi, lo), S_m, Jm (hi, lo), S_J).  S: how far the exact result moves when q moves
@@ -244,48 +223,10 @@ def worst(name, m, Jm):
             max(ratio(Jm[b], ref[b][2], ref[b][3]) for b in range(len(ref))))
 
 
-# ---- measured ratios (profiles/manipulability_exact.json) -----------------------------------------------------------------
-RATIOS = {}
-
-
-def note_ratios(who, name, rm, rj):
-    d = RATIOS.setdefault(who, {})
-    d[name + "_m"], d[name + "_J"] = max(d.get(name + "_m", 0.0), float(rm)), max(d.get(name + "_J", 0.0), float(rj))
-
-
-def write_ratios():
-    """PINK_MANIPULABILITY_RATIOS=<file>: the worst ratios noted so far are merged into that JSON file, one block per
-    "host" / "emu" / "gpu", beside the bar of every case (``bar``) and the unit."""
-    path = os.environ.get("PINK_MANIPULABILITY_RATIOS")
-    if not path or not RATIOS:
-        return
-    have = {}
-    if os.path.exists(path):
-        with open(path) as f:
-            have = json.load(f)
-    for who, d in RATIOS.items():
-        have[who] = {n: float("%.3g" % v) for n, v in sorted(d.items())}
-    have["bar"] = {n: bar(n) for n in sorted(CASES)}
-    have["unit"] = ("what one ulp on q does to the exact result + eps max|exact| (tests/manipulability_cases.py); <case>_m: the "
-                    "manipulability, <case>_J: its gradient")
-    with open(path, "w") as f:
-        json.dump(have, f, indent=1, sort_keys=True)
-        f.write("\n")
-
-
-# ---- the emulator behind BatchSolver.manipulability_task --------------------------------------------------------------------
-def with_manipulability(api):
-    if hasattr(api, "manipulability_task"):
-        return api
-    lib, vp, ll, ci = api.lib, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
-    lib.pinkhip_emu_manipulability_task.argtypes = [vp, ll, vp, ci, ci, ci, ctypes.c_double, vp, ll, vp, ll, ci, vp]
-    lib.pinkhip_emu_last_error.restype = ctypes.c_char_p
-
-    def manipulability_task(model, B, q, frame, reference_frame, row_mask, rate, e, sE, J, sJ, row0, m_out=None):
-        rc = lib.pinkhip_emu_manipulability_task(model, B, q, int(frame), int(reference_frame), int(row_mask), float(rate), e, sE, J, sJ,
-                                                 int(row0), m_out)
-        if rc != 0:
-            raise PinkHipError(rc, lib.pinkhip_emu_last_error().decode())
-
-    api.manipulability_task = manipulability_task
-    return api
+# ---- measured ratios: PINK_MANIPULABILITY_RATIOS=<file> (profiles/manipulability_exact.json), beside the bar of every case
+# and the unit ---------------------------------------------------------------------------------------------------------------
+_UNIT = ("what one ulp on q does to the exact result + eps max|exact| (tests/manipulability_cases.py); <case>_m: the "
+         "manipulability, <case>_J: its gradient")
+_RECORDER = RatioRecorder("PINK_MANIPULABILITY_RATIOS", "profiles/manipulability_exact.json", ("m", "J"),
+                          extra=lambda: {"bar": {n: bar(n) for n in sorted(CASES)}, "unit": _UNIT})
+RATIOS, note_ratios, write_ratios = _RECORDER.noted, _RECORDER.note, _RECORDER.write

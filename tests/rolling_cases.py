@@ -10,6 +10,9 @@ session, shared by all of them.
           the hub of wheel 2 sits on a knee, so the joint below it on the same leg is off its path
   tree34  the 34-joint tree with free-flyer of tests/com_task_cases.py (one robot per wavefront); two wheels on leaves of
           unequal depth; the floor of the second hangs on a moving joint of another branch
+  chain8, chain32  the serial revolute chains of tests/com_task_cases.py, nj = W = 8 and 32 (the deepest tree a group admits, no
+          idle lane, a partial last wavefront at B = 9 and 3); a Rolling wheel with its hub on the last joint and its floor on
+          the world, an Omniwheel whose floor hangs on joint 2, an ancestor of its hub
 
 Magnitudes -- a condition, not a taste.  Hub frames carry a placement that is not the identity, radii lie in [0.05, 0.3]
 beside link lengths of 0.3, floors are tilted by at least 0.3 rad, revolute joints make several turns, prismatic ones move
@@ -19,24 +22,22 @@ far more than the bar: :func:`term_moves` drops each term from the 60-digit rows
 tests/test_rolling_task.py::test_every_term_is_worth_100_bars holds the change to at least 100 bars on every instance of
 every model the term applies to.
 """
-import ctypes
 import functools
-import json
 import os
 
 import mpmath as mp
 import numpy as np
 
 from oracle import exact_kinematics as ek
-from pink_amd._lib import PinkHipError
 from pink_amd.configuration import Model
 from pink_amd.lie import SE3, exp3
 from pink_amd.rollout import ModelArrays
 from pink_amd.tasks import OmniwheelTask, RollingTask
-from tests.com_task_cases import tree
+from tests.com_task_cases import chain, tree
+from tests.row_kernel_kit import EPS, RatioRecorder, _split, random_configurations, ratio, with_rolling  # noqa: F401 (re-exported)
+from tests.row_kernel_kit import cross as _cross
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EPS = 2.0 ** -52
 K_ROLL = 8.0  # the bar tests/test_kinematics_exact.py holds poses and body Jacobians to
 ROLLING, OMNI = 0, 1
 HUB = SE3(exp3([0.2, -0.3, 0.25]), [0.02, -0.03, 0.04])  # placement of a hub frame on its joint
@@ -121,14 +122,24 @@ def _tree34():
     return m, [(OMNI, "hub_a", "ramp", 0.25), (ROLLING, "hub_b", "deck", 0.08)]
 
 
+def _chain(n):
+    m = chain(n, n)
+    m.add_frame("hub_a", n - 1, HUB)
+    m.add_frame("ramp", -1, TILT)
+    m.add_frame("hub_b", n - 3, SE3(exp3([-0.3, 0.1, 0.2]), [0.01, 0.04, -0.02]))
+    m.add_frame("deck", 2, SE3(exp3([0.3, 0.3, -0.2]), [0.1, 0.0, -0.1]))  # a floor that moves with q, below its hub
+    return m, [(ROLLING, "hub_a", "ramp", 0.12), (OMNI, "hub_b", "deck", 0.2)]
+
+
 @functools.lru_cache(maxsize=None)
 def models():
     """name -> (model, wheels); a wheel is (kind, hub frame, floor frame, radius)."""
-    return {"cart": _cart(), "biped": _biped(), "quad": _quad(), "tree34": _tree34()}
+    return {"cart": _cart(), "biped": _biped(), "quad": _quad(), "tree34": _tree34(), "chain8": _chain(8), "chain32": _chain(32)}
 
 
-BATCH = {"cart": 11, "biped": 11, "quad": 3, "tree34": 2}
-WIDTH = {"cart": 8, "biped": 8, "quad": 32, "tree34": 64}  # lanes per robot: the smallest of 8 / 32 / 64 that holds nj
+BATCH = {"cart": 11, "biped": 11, "quad": 3, "tree34": 2, "chain8": 9, "chain32": 3}
+# lanes per robot: the smallest of 8 / 32 / 64 that holds nj
+WIDTH = {"cart": 8, "biped": 8, "quad": 32, "tree34": 64, "chain8": 8, "chain32": 32}
 
 
 def tasks_of(name, cost=1.0, **kw):
@@ -150,26 +161,10 @@ def configurations(name, B=None, seed=7):
     quaternions with w < 0."""
     model = models()[name][0]
     B = BATCH[name] if B is None else B
-    rng = np.random.default_rng(seed + len(name))
-    q = np.zeros((B, model.nq))
-    for j in model.joints:
-        if j.kind == "free_flyer":
-            q[:, j.idx_q:j.idx_q + 3] = rng.normal(size=(B, 3))
-            qu = rng.normal(size=(B, 4))
-            qu[:, 3] = -np.abs(qu[:, 3]) - 0.1
-            q[:, j.idx_q + 3:j.idx_q + 7] = qu / np.linalg.norm(qu, axis=1, keepdims=True)
-        elif j.kind == "prismatic":
-            q[:, j.idx_q] = rng.uniform(-0.5, 0.5, size=B)
-        else:
-            q[:, j.idx_q] = rng.uniform(-6.0, 6.0, size=B)
-    return q
+    return random_configurations(model, B, np.random.default_rng(seed + len(name)))
 
 
 # ---- the 60-digit reference ---------------------------------------------------------------------------------------------
-def _cross(a, b):
-    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
-
-
 def _pose_of(oM, joint, placement12):
     P = ek.pose_matrix(placement12)
     return P if joint < 0 else ek.mm(oM[joint], P)
@@ -229,21 +224,6 @@ def exact_rows(t, q, kinds, radii, drop=None):
         J += [Jw[r] for r in keep]
         zs.append(z)
     return e, J, zs
-
-
-def _split(ref):
-    fl = ek.flat(ref)
-    hi = np.array([float(x) for x in fl])
-    with mp.workdps(ek.DPS):
-        lo = np.array([float(x - mp.mpf(h)) for x, h in zip(fl, hi)])
-    return hi, lo
-
-
-def ratio(dev, ref, S):
-    """Error in units of u = S + eps max|reference| (tests/test_kinematics_exact.py)."""
-    hi, lo = ref
-    u = S + EPS * np.abs(hi).max()
-    return float(np.abs((np.asarray(dev, dtype=np.float64).ravel() - hi) - lo).max() / u)
 
 
 def _fn(arr, kinds):
@@ -330,50 +310,6 @@ def term_moves(name):
     return out
 
 
-# ---- measured ratios (profiles/rolling_task_exact.json) -----------------------------------------------------------------------
-RATIOS = {}
-
-
-def note_ratios(who, name, re, rj, rz=None):
-    d = RATIOS.setdefault(who, {})
-    for key, v in (("e", re), ("J", rj), ("z", rz)):
-        if v is not None:
-            d[f"{name}_{key}"] = max(d.get(f"{name}_{key}", 0.0), float(v))
-
-
-def write_ratios():
-    """PINK_ROLLING_TASK_RATIOS=<file>: the worst ratios noted so far are merged into that JSON file, one block per
-    "host" / "reference" / "emu" / "gpu" (the host tests and the device tests of one session, and a later GPU session, add
-    theirs)."""
-    path = os.environ.get("PINK_ROLLING_TASK_RATIOS")
-    if not path or not RATIOS:
-        return
-    have = {}
-    if os.path.exists(path):
-        with open(path) as f:
-            have = json.load(f)
-    for who, d in RATIOS.items():
-        have.setdefault(who, {}).update({n: float("%.3g" % v) for n, v in sorted(d.items())})
-    with open(path, "w") as f:
-        json.dump(have, f, indent=1, sort_keys=True)
-        f.write("\n")
-
-
-# ---- the emulator behind BatchSolver.rolling_tasks --------------------------------------------------------------------------
-def with_rolling(api):
-    """The emulator behind BatchSolver's ``rolling_tasks`` (pinkhip_rolling_tasks_device's twin on host memory)."""
-    if hasattr(api, "rolling_tasks"):
-        return api
-    lib, vp, ll, ci = api.lib, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
-    lib.pinkhip_emu_rolling_tasks.argtypes = [vp, ll, vp, ci, vp, vp, vp, vp, ll, vp, ll, ci, vp]
-    lib.pinkhip_emu_last_error.restype = ctypes.c_char_p
-
-    def rolling_tasks(model, B, q, slots, kinds, radii, e, sE, J, sJ, row0, height_out=None):
-        n = len(slots)
-        s, k, r = (None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in ((slots, np.int32), (kinds, np.int32), (radii, np.float64)))
-        rc = lib.pinkhip_emu_rolling_tasks(model, B, q, n, *(None if a is None else a.ctypes.data for a in (s, k, r)), e, sE, J, sJ, int(row0), height_out)
-        if rc != 0:
-            raise PinkHipError(rc, lib.pinkhip_emu_last_error().decode())
-
-    api.rolling_tasks = rolling_tasks
-    return api
+# ---- measured ratios: PINK_ROLLING_TASK_RATIOS=<file> (profiles/rolling_task_exact.json) -------------------------------------------
+_RECORDER = RatioRecorder("PINK_ROLLING_TASK_RATIOS", "profiles/rolling_task_exact.json", ("e", "J", "z"), merge=True)
+RATIOS, note_ratios, write_ratios = _RECORDER.noted, _RECORDER.note, _RECORDER.write

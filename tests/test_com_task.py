@@ -33,6 +33,9 @@ def test_models_are_what_the_device_tests_need():
     assert abs(t.joints[8].mass / t.total_mass - 0.8) < 1e-12 and not any(j.parent == 8 for j in t.joints)
     assert sum(j.kind == "prismatic" for j in t.joints) == 1
     assert m["tree34"][0].nv == 39 and m["tree34"][0].joints[0].kind == "free_flyer"
+    for n in (8, 32):  # the chains: serial (depth = nj = the group width), all revolute, every joint with a mass
+        c = m[f"chain{n}"][0]
+        assert [j.parent for j in c.joints] == list(range(-1, n - 1)) and all(j.kind == "revolute" and j.mass > 0.0 for j in c.joints)
 
 
 def test_default_models_stay_massless():
@@ -97,7 +100,7 @@ def test_the_moved_joint_follows_exact_kinematics_integrate():
             assert max(abs(a - b) for a, b in zip(ek.flat(want), ek.flat(got))) < mp.mpf(10) ** -55
 
 
-@pytest.mark.parametrize("name", ["arm6", "tree12", "tree34", "pend"])
+@pytest.mark.parametrize("name", ["arm6", "tree12", "tree34", "pend", "chain8", "chain32"])
 def test_host_centre_of_mass_and_jacobian_against_60_digits(name):
     model, _ = models()[name]
     q, _ = reference(name)

@@ -55,7 +55,7 @@ def device_rows(api, name, q, target, sE=None, sJ=None, row0=0, with_com_out=Tru
 
 
 # ---- 1. exact anchor --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["arm6", "tree12", "tree34", "pend"])
+@pytest.mark.parametrize("name", ["arm6", "tree12", "tree34", "pend", "chain8", "chain32"])
 def test_rows_against_60_digits(api, name):
     """com and J within K_COM = 8 units of u = S + eps max|exact| (what one ulp on the inputs does to the exact result);
     e = com - target to the rounding of that one subtraction."""
@@ -83,7 +83,7 @@ def test_rows_against_60_digits(api, name):
 
 
 # ---- 2. only its rows -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["arm6", "tree12", "tree34"])
+@pytest.mark.parametrize("name", ["arm6", "tree12", "tree34", "chain8", "chain32"])
 def test_only_its_rows_are_written(api, name):
     """Strides larger than natural, row0 = 6: exactly 3 entries of e and 3 nv of J per instance change -- the lanes of a
     padded group (columns j >= nv, robots b >= B of the last wavefront) write nothing."""

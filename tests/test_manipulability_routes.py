@@ -10,13 +10,13 @@ from pink_amd import ComTask, Configuration, ConfigurationBatch, FrameTask, Mani
 from pink_amd.exceptions import PinkError
 from pink_amd.lie import exp6
 from pink_amd.runtime import set_default_solver
-from tests.com_task_cases import with_com
-from tests.manipulability_cases import cond_A, models, with_manipulability
+from tests.manipulability_cases import cond_A, models
+from tests.row_kernel_kit import with_row_kernels
 
 
 @pytest.fixture(params=["emu", pytest.param("gpu", marks=pytest.mark.gpu)])
 def backend(request):
-    s = with_manipulability(with_com(request.getfixturevalue("emu" if request.param == "emu" else "gpu_solver")))
+    s = with_row_kernels(request.getfixturevalue("emu" if request.param == "emu" else "gpu_solver"))
     set_default_solver(s)
     yield s
     pink_amd.clear_device_cache()

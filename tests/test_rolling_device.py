@@ -12,7 +12,7 @@ from tests.rolling_cases import (K_ROLL, OMNI, ROLLING, WIDTH, arrays, configura
                                  with_rolling, worst, write_ratios)
 
 SENTINEL = -7.25e300
-NAMES = ["cart", "biped", "quad", "tree34"]
+NAMES = ["cart", "biped", "quad", "tree34", "chain8", "chain32"]
 
 
 @pytest.fixture(params=["emu", pytest.param("gpu", marks=pytest.mark.gpu)])

@@ -11,15 +11,15 @@ from pink_amd import ComTask, Configuration, ConfigurationBatch, FrameTask, Omni
 from pink_amd.exceptions import PinkError
 from pink_amd.lie import exp6
 from pink_amd.runtime import set_default_solver
-from tests.com_task_cases import with_com
-from tests.rolling_cases import configurations, models, tasks_of, with_rolling
+from tests.rolling_cases import configurations, models, tasks_of
+from tests.row_kernel_kit import with_row_kernels
 
 B, DT = 11, 5e-3
 
 
 @pytest.fixture(params=["emu", pytest.param("gpu", marks=pytest.mark.gpu)])
 def api(request):
-    s = with_rolling(with_com(request.getfixturevalue("emu" if request.param == "emu" else "gpu_solver")))
+    s = with_row_kernels(request.getfixturevalue("emu" if request.param == "emu" else "gpu_solver"))
     set_default_solver(s)
     yield s
     pink_amd.clear_device_cache()

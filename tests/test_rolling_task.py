@@ -13,7 +13,7 @@ from pink_amd.runtime import set_default_solver
 from tests.rolling_cases import (arrays, configurations, models, note_ratios, reference, reference_bar, tasks_of,
                                  term_moves, worst, write_ratios)
 
-NAMES = ["cart", "biped", "quad", "tree34"]
+NAMES = ["cart", "biped", "quad", "tree34", "chain8", "chain32"]
 
 
 @pytest.fixture(scope="module", autouse=True)
