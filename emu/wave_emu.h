@@ -116,6 +116,7 @@ inline void pin(T &) {}
 inline void opaque(double &) {}
 inline void forget(double &) {}  // (the device code declares the value dead; here it simply stays)
 inline int opaque_uniform(int x) { return x; }
+inline unsigned opaque_offset(unsigned x) { return x; }
 template <class Args>
 inline const Args *kernarg_reload(const Args &a) {
   return &a;

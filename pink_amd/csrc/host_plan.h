@@ -154,6 +154,14 @@ inline int plan_stack(const KernelArgs &a, bool four_tiles, LaunchPlan &p, std::
   return PINKHIP_OK;
 }
 
+// The sweep-tableau stack + solve kernels address the task rows of a wavefront's 64 / W instances with ONE 32-bit byte offset
+// per lane from a scalar base (ik_stack_rows.h: WaveSplit, FULL_CHUNKS): those rows must lie within 4 GiB.  (2 GiB of task
+// rows per instance at W = 32: no stack of Pink's comes near it; a batch that does runs the Goldfarb-Idnani kernel, which
+// addresses in 64 bits per lane.)
+inline bool rows_within_lane_offset(const KernelArgs &a, int W) {
+  return W > 0 && (64 / W) * static_cast<long long>(a.Kd) * a.nv * 8 < (1LL << 32);
+}
+
 // Stack + solve: the instantiation chosen by dispatch.h.  The sweep-tableau kernel (ik_sweep.h) serves every problem it
 // is instantiated for -- with virtual dense rows where that packs more QPs into a wavefront (ik_sweepx.h, prefer_sweepx)
 // -- and the Goldfarb-Idnani kernel (ik_kernels_packed.h) the rest: 8-lane groups (nv <= 8), more dense rows than lanes
@@ -171,12 +179,14 @@ inline int plan_solve(const KernelArgs &a, const char *solver_env, bool force_de
   if (a.B == 0) return PINKHIP_OK;
   if (a.B > 0x7fffffffLL) return refuse(err, PINKHIP_E_INVALID, "B exceeds the grid limit 2^31-1");
   if (warm) {
+    if (!rows_within_lane_offset(a, wc.W)) return refuse(err, PINKHIP_E_UNSUPPORTED, "the task rows of a wavefront exceed 4 GiB: no warm start");
     p = make_plan(PLAN_SWEEP_WARM, wc.NV, wc.MD, wc.W, 0, a.B);
     return PINKHIP_OK;
   }
   const SweepChoice sc = select_sweep(a.nv, a.md, a.n_free_lead);
-  const bool sweep = solver_env ? (std::strcmp(solver_env, "packed") != 0 && sc.NV != 0)
-                                : (prefer_sweep(a.nv, a.md, a.B, a.n_free_lead) && !a.rank_deficient);
+  const bool sweep = (solver_env ? (std::strcmp(solver_env, "packed") != 0 && sc.NV != 0)
+                                 : (prefer_sweep(a.nv, a.md, a.B, a.n_free_lead) && !a.rank_deficient)) &&
+                     rows_within_lane_offset(a, sc.W);
   const SweepChoice xc = select_sweepx(a.nv, a.md);
   const bool sweepx = solver_env ? (std::strcmp(solver_env, "sweepx") == 0 && xc.NV != 0) : (prefer_sweepx(a.nv, a.md) && !a.rank_deficient);
   const PackedChoice pc = select_packed(a.nv, a.md);

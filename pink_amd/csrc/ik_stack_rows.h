@@ -66,7 +66,7 @@ struct WaveSplit {
 #ifndef PINKHIP_WAVE_SPLIT
 #define PINKHIP_WAVE_SPLIT(Src) (!Src::kOnTheFly)
 #endif
-// Two switches of the stacking that remove work and change no bit of any result, on where the streams are addressed through
+// Three switches of the stacking that remove work and change no bit of any result, on where the streams are addressed through
 // a WaveSplit (DIAG below: the stack + solve kernels with rows from HBM); off, the device code is what it was.
 //   ROLE_BUFFERS     the chunk loop is unrolled by the number of chunk buffers, so that a buffer changes its ROLE from trip to
 //                    trip -- requested into, accumulated from -- instead of being copied into its neighbour at the end of
@@ -99,13 +99,31 @@ struct WaveSplit {
 #ifndef PINKHIP_STACK_SKIP_ZERO_ROWS
 #define PINKHIP_STACK_SKIP_ZERO_ROWS(Src) PINKHIP_WAVE_SPLIT(Src)
 #endif
+//   FULL_CHUNKS      a chunk that is full (Kd - r0 >= RC, wave-uniform: every chunk of the headline's 24 rows) is requested
+//                    without the per-row `kk < rc`: ONE region of the lanes `in` around its RC row loads, the row's address a
+//                    scalar pointer that advances by the run-time pitch (nv doubles) from row to row -- no (r0 + kk) * nv per
+//                    row -- and this lane's part the 32-bit BYTE offset 8 voJ, so that the load takes the scalar base and
+//                    the 32-bit offset as they are (global_load_dwordx2 v, v, s[:]) instead of a 64-bit sum per lane and
+//                    row.  The same loads from the same addresses (8 voJ < 2^32: the instances of a wave hold less than
+//                    4 GiB of task rows -- host_plan.h: rows_within_lane_offset sends anything else to another kernel); the
+//                    lanes li >= nv get their zeros as before.  A partial chunk -- the last one of a Kd that is no multiple
+//                    of RC -- makes the requests it always made, inside the same region: `kk < rc` is a scalar branch there.
+//                    The weights, errors, gains, LM factors and front columns are requested as they were, by the lanes
+//                    li < rc: on a full chunk that guard is one s_min and one v_cmp, and a second copy of those requests for
+//                    `li < RC` would stand next to the first as the two forms of the row requests first did (request()).
+//                    Needs ROLE_BUFFERS (the buffers keep their registers).
+#ifndef PINKHIP_STACK_FULL_CHUNKS
+#define PINKHIP_STACK_FULL_CHUNKS(Src) PINKHIP_WAVE_SPLIT(Src)
+#endif
 // DIAG: *hdiag follows this lane's own diagonal entry M[li] (lane li, li < NV) in a register of its own -- the product the
 // broadcast-FMA of column li forms in lane li is this lane's own row entry times its own factor: the same FMA on the
 // same operands, bit for bit what M[li] receives -- so that the caller does not have to pick "register li of lane li"
 // out of the row afterwards (NV compares and 2 NV selects).  It also takes the instance as `ws` (b = ws.first + ws.rel)
 // and addresses the streams as described at WaveSplit: the same addresses.  Off: nothing changes.
-// ROLE_OK: the caller's veto of ROLE_BUFFERS for an instantiation in which the unrolled loop costs registers.
-template <int NV, int W, int RCMAX, class Src, int DEPTH = 1, int NX = 0, bool DIAG = false, bool ROLE_OK = true, int NM, class Mid = NoMid>
+// ROLE_OK, FULL_OK: the caller's veto of ROLE_BUFFERS / FULL_CHUNKS for an instantiation in which the unrolled loop / the second
+// form of the requests costs registers.
+template <int NV, int W, int RCMAX, class Src, int DEPTH = 1, int NX = 0, bool DIAG = false, bool ROLE_OK = true, bool FULL_OK = true, int NM,
+          class Mid = NoMid>
 __device__ __forceinline__ void stack_rows_bcast(const KernelArgs &a, long long b, Src *terms, bool in, int li,
                                                  double (&M)[NM], double &ci, double &mu_l, Mid mid = Mid(), StackFront<NX> *front = nullptr,
                                                  double *hdiag = nullptr, WaveSplit ws = WaveSplit()) {
@@ -117,10 +135,12 @@ __device__ __forceinline__ void stack_rows_bcast(const KernelArgs &a, long long 
   constexpr bool SPLIT = DIAG && PINKHIP_WAVE_SPLIT(Src);
   constexpr bool ROLES = SPLIT && ROLE_OK && PINKHIP_STACK_ROLE_BUFFERS(Src);
   constexpr bool ZSKIP = SPLIT && PINKHIP_STACK_SKIP_ZERO_ROWS(Src);
+  constexpr bool FULL = ROLES && FULL_OK && !Src::kOnTheFly && PINKHIP_STACK_FULL_CHUNKS(Src);  // (the buffers keep their registers)
   const double *Jb = a.J + (SPLIT ? ws.first : b) * (long long)Kd * nv;
   const double *eb = a.e + (SPLIT ? ws.first : b) * (long long)K;
   const double *costb = a.cost_batched ? a.cost + (SPLIT ? ws.first : b) * (long long)K : a.cost;
   const unsigned voJ = SPLIT ? ws.rel * static_cast<unsigned>(Kd * nv) + li : 0u;
+  const unsigned voJ8 = voJ * 8u;  // (FULL: in bytes)
   const unsigned voE = SPLIT ? ws.rel * static_cast<unsigned>(K) + li : 0u;
   const unsigned voC = (SPLIT && a.cost_batched) ? voE : static_cast<unsigned>(li);
   constexpr int RC = Src::kOnTheFly ? 6 : (RCMAX < 8 ? RCMAX : 8);
@@ -132,13 +152,40 @@ __device__ __forceinline__ void stack_rows_bcast(const KernelArgs &a, long long 
     double px[NX > 0 ? NX : 1];
   };
   Chunk buf[NB];
-  auto request = [&](Chunk &dst, int r0) {
+  // (hold: the request is made inside the chunk loop -- FULL: this lane's offset is pinned there, wave.h: opaque_offset)
+  auto request = [&](Chunk &dst, int r0, bool hold = false) {
     const int rc = (Kd - r0 < RC) ? Kd - r0 : RC;  // (<= 0: past the end, nothing is read)
     if constexpr (Src::kOnTheFly) {
       double six[6];
       terms->frame_rows(r0 / 6, six);
 #pragma unroll
       for (int kk = 0; kk < RC; ++kk) dst.r[kk] = (in && kk < rc) ? six[kk] : 0.0;
+    } else if constexpr (FULL) {
+      // The defaults first, for every lane; then ONE region of the lanes `in`, and inside it nothing but wave-uniform
+      // branches: the full chunk's RC loads from a scalar row pointer, or the rows kk < rc of a partial one.  (The two
+      // forms side by side, each with its own region of lanes and its own defaults, are linearised one behind the other, and
+      // the defaults of the second then follow, as far as the wait counters can tell, the loads of the first into the same
+      // registers: every request waited for everything in flight.)
+#pragma unroll
+      for (int kk = 0; kk < RC; ++kk) dst.r[kk] = 0.0;
+      if (in) {
+        if (Kd - r0 >= RC) {  // a full chunk
+          const char *row = reinterpret_cast<const char *>(Jb + (long long)r0 * nv);  // (scalar)
+          const long long pitch = (long long)nv * 8;
+          // (pinned in the loop only: in front of it the offset is formed next to the load anyway, and a volatile asm ahead of
+          // `mid` would cost its table reads their scalar loads)
+          const unsigned vo8 = hold ? opaque_offset(voJ8) : voJ8;
+#pragma unroll
+          for (int kk = 0; kk < RC; ++kk) {
+            dst.r[kk] = *reinterpret_cast<const double *>(row + vo8);
+            row += pitch;
+          }
+        } else {
+#pragma unroll
+          for (int kk = 0; kk < RC; ++kk)
+            if (kk < rc) dst.r[kk] = (Jb + (long long)(r0 + kk) * nv)[voJ];
+        }
+      }
     } else {
 #pragma unroll
       for (int kk = 0; kk < RC; ++kk) {
@@ -305,7 +352,7 @@ __device__ __forceinline__ void stack_rows_bcast(const KernelArgs &a, long long 
           if (r < Kd) {  // wave-uniform
             // (no request: the buffer's registers are dead, and said to be -- carried round the loop as they were, a row's
             // permlane swaps would have to spare them: two more v_mov_b32 per row)
-            if (r + (NB - 1) * RC < Kd) request(buf[(s + NB - 1) % NB], r + (NB - 1) * RC);
+            if (r + (NB - 1) * RC < Kd) request(buf[(s + NB - 1) % NB], r + (NB - 1) * RC, true);
             else forget_chunk(buf[(s + NB - 1) % NB]);
             accumulate(buf[s], r);
           } else {

@@ -75,6 +75,15 @@ static __device__ unsigned long long pinkhip_clock[16];  // one copy per transla
 #ifndef PINKHIP_SWEEP_STACK_ROLE_BUFFERS
 #define PINKHIP_SWEEP_STACK_ROLE_BUFFERS(NV, MD, W) (!((NV) == 30 && (MD) == 8 && (W) == 64))
 #endif
+// full chunks of task rows requested from one scalar row base (ik_stack_rows.h: FULL_CHUNKS) -- not from NV = 50 on: with
+// two chunks ahead and 50 or more registers of row the second form of the requests spills (<50, 6, 64> 0 -> 16 VGPRs,
+// <50, 14, 64> 0 -> 32, <56, 0, 64> 4 -> 18, <56, 8, 64> 32 -> 64, <64, 0, 64> 0 -> 28, the warm <50, 0, 64> 0 -> 2 and
+// <64, 0, 64> 0 -> 30; up to <48, 0, 64> no instantiation spills a register more than it did -- the four below that run two
+// chunks ahead grow in registers at unchanged occupancy, two waves per SIMD: <34, 8, 64> 227 -> 244 VGPRs, <40, 0, 64>
+// 197 -> 235, <40, 8, 64> 247 -> 256, <48, 0, 64> 227 -> 251, SGPRs 104 -> 106; none of those shapes has been timed)
+#ifndef PINKHIP_SWEEP_STACK_FULL_CHUNKS
+#define PINKHIP_SWEEP_STACK_FULL_CHUNKS(NV, MD, W) ((NV) < 50)
+#endif
 // Column p of the tableau (group-uniform run-time p) read with the VGPR index mode from register tuples (TabRegs,
 // ik_common.h) instead of NT broadcast-FMAs against the indicator of p: groups of 32 and 64 lanes (one or two reads per
 // wave; four groups of 16 lanes would pay as much as the FMAs they replace)
@@ -302,9 +311,9 @@ __device__ __forceinline__ int ik_sweep_instance(const KernelArgs &a, long long 
   if constexpr (NE > 0) {
     KernelArgs af = a;  // (the rows as the lanes see them: NE columns in)
     af.J = a.J + NE;
-    stack_rows_bcast<NV, W, 8, Src, PINKHIP_STACK_DEPTH, NE, DREG, PINKHIP_SWEEP_STACK_ROLE_BUFFERS(NVT, MD, W)>(af, b, terms, in, li, T, ci, mu_l, others, &front, &hii, ws);
+    stack_rows_bcast<NV, W, 8, Src, PINKHIP_STACK_DEPTH, NE, DREG, PINKHIP_SWEEP_STACK_ROLE_BUFFERS(NVT, MD, W), PINKHIP_SWEEP_STACK_FULL_CHUNKS(NVT, MD, W)>(af, b, terms, in, li, T, ci, mu_l, others, &front, &hii, ws);
   } else {
-    stack_rows_bcast<NV, W, 8, Src, (NT > 34 ? PINKHIP_STACK_DEPTH_WIDE : PINKHIP_STACK_DEPTH), 0, DREG, PINKHIP_SWEEP_STACK_ROLE_BUFFERS(NVT, MD, W)>(a, b, terms, in, li, T, ci, mu_l, others, nullptr, &hii, ws);
+    stack_rows_bcast<NV, W, 8, Src, (NT > 34 ? PINKHIP_STACK_DEPTH_WIDE : PINKHIP_STACK_DEPTH), 0, DREG, PINKHIP_SWEEP_STACK_ROLE_BUFFERS(NVT, MD, W), PINKHIP_SWEEP_STACK_FULL_CHUNKS(NVT, MD, W)>(a, b, terms, in, li, T, ci, mu_l, others, nullptr, &hii, ws);
   }
   ci += ci_d;
   mu_l += mu_d;

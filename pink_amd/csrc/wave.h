@@ -172,6 +172,13 @@ __device__ __forceinline__ int opaque_uniform(int x) {
   return x;
 }
 
+// ... and a 32-bit per-lane offset.  Its zero extension is then formed where the offset is used, next to the scalar base, and a
+// load takes the pair as it is (global_load v, v, s[:]); hoisted out of a loop as a 64-bit value it costs a 64-bit sum per load.
+__device__ __forceinline__ unsigned opaque_offset(unsigned x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
 // Pin two groups of eight values at once: the sixteen loads that produce them are all issued
 // before this point and waited for once (hipcc otherwise issues the LDS reads of an accumulation
 // chain pairwise, right before their use, and every pair pays the full LDS latency).
