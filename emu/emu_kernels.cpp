@@ -256,6 +256,29 @@ int pinkhip_emu_rolling_joint_check(int nj) {
   if (const char *bad = pinkhip::rolling_task_fault(a, root_joint, code)) return pinkhip::refuse(g_err, code, bad);
   return PINKHIP_OK;
 }
+// the barrier rows, mirroring pinkhip_barrier_rows_device on host memory
+int pinkhip_emu_barrier_rows(void *mp, long long B, const double *q, double dt, const pinkhip_barrier_rows *rows,
+                             const pinkhip_sphere_pairs *pairs, double *Gd, long long sG, double *hd, long long sH, int row0, double *dist_out) {
+  if (!mp) return pinkhip::refuse(g_err, PINKHIP_E_INVALID, "null handle / model");
+  const EmuModel *m = static_cast<const EmuModel *>(mp);
+  pinkhip::BarrierRowsArgs a;
+  if (const int rc = pinkhip::plan_barrier_rows(m->dev, B, q, dt, rows, pairs, Gd, sG, hd, sH, row0, dist_out, a, g_err)) return rc;
+  if (B == 0) return PINKHIP_OK;
+  return run_fk(pinkhip::barrier_rows_group_width(m->dev.nj), B, lane_main_barrier_rows<8>, lane_main_barrier_rows<32>, lane_main_barrier_rows<64>, &a);
+}
+// Test infrastructure: the joint-count refusal on a bare count, without a device model in front of it (a model of more than
+// 64 joints cannot be created: nv <= PINKHIP_MAX_NV)
+int pinkhip_emu_barrier_rows_joint_check(int nj) {
+  g_err.clear();
+  pinkhip::ModelDev md{};
+  md.nj = nj;
+  md.nv = 1;
+  const int frame[1] = {0};
+  const double one[1] = {1.0};
+  pinkhip_barrier_rows rows{1, frame, frame, frame, one, one, one};
+  pinkhip::BarrierRowsArgs a;
+  return pinkhip::plan_barrier_rows(md, 0, nullptr, 1e-3, &rows, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, a, g_err);
+}
 int pinkhip_emu_step(void *mp, long long B, const pinkhip_step *st) {
   EmuModel *m = static_cast<EmuModel *>(mp);
   pinkhip::FkArgs a = pinkhip::step_args(m->dev, B, *st);

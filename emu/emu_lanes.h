@@ -16,6 +16,7 @@
 #include "../pink_amd/csrc/ik_manip.h"
 #include "../pink_amd/csrc/ik_rolling.h"
 #include "../pink_amd/csrc/ik_rollout.h"
+#include "../pink_amd/csrc/ik_barrier_rows.h"
 #include "../pink_amd/csrc/model_tables.h"
 #include "../pink_amd/csrc/host_tables.h"
 // clang-format on
@@ -90,6 +91,11 @@ void lane_main_manip(void *p) {
 template <int W>
 void lane_main_rolling(void *p) {
   pinkhip::ik_rolling_instance<W>(*static_cast<const pinkhip::RollingArgs *>(p), pinkhip::block_id());
+}
+
+template <int W>
+void lane_main_barrier_rows(void *p) {
+  pinkhip::ik_barrier_rows_instance<W>(*static_cast<const pinkhip::BarrierRowsArgs *>(p), pinkhip::block_id());
 }
 
 }  // namespace pinkemu

@@ -508,6 +508,43 @@ int pinkhip_rolling_tasks_device(pinkhip_handle *h, const pinkhip_model *model, 
                                  const double *radius /* [n] host */, double *e, int64_t sE, double *J, int64_t sJ,
                                  int32_t row0, double *height_out /* [B, n] device or NULL: z per wheel */);
 
+/* ---- Barrier rows (pink/barriers/position_barrier.py, body_spherical_barrier.py, self_collision_barrier.py), formed on the device ----
+ * The dense inequality rows of barriers, written in the form pinkhip_solve_device consumes (pink/barriers/barrier.py:246-254):
+ * for every instance b and row r of the call
+ *     Gd[b sG + (row0 + r) nv + j] = -J_h[r][j] / dt        j = 0..nv-1
+ *     hd[b sH + row0 + r]          = gain alpha(h_r)
+ * With sG = md nv and sH = md the rows land in pinkhip_problem.Gd / .hd behind the equality and limit rows.  The tables and
+ * conventions are those of pinkhip_rollout_step's barrier_* tables and of pinkhip_sphere_pairs, so a caller passes the same
+ * device tables to either call.  rows->n_rows rows come first, row r described by (frame, axis, frame2, sign, bound, gain)[r]:
+ *     axis 0..2   PositionBarrier row: h = sign (p_f[axis] - bound) with p_f the world position of the origin of frame slot
+ *                 f = frame[r] of the model, J_h = sign times row `axis` of the world-aligned linear Jacobian of that origin,
+ *                 identity class-K function; frame2 is ignored (-1 by convention)
+ *     axis 3      BodySphericalBarrier row: d = p_f - p_f2, h = |d|^2 - bound (bound = d_min^2), alpha(h) = h / (1 + |h|),
+ *                 J_h = 2 d^T (Jlin_f - Jlin_f2); sign is ignored
+ * then, when pairs is not NULL, the pairs->n_rows sphere-pair rows of pinkhip_rollout_step_pairs_device: the pairs with the
+ * smallest distances, ascending, ties to the lower pair index; G = -J / dt, J_i = n . (v_i(c_a) - v_i(c_b)),
+ * h = gain (dist - d_min); a zero row where the nearest points coincide to np.allclose's tolerances.  dist_out [B, pairs->n_rows]
+ * (may be NULL) receives the selected distances.  These rows are written completely -- columns of joints off a frame's (a
+ * sphere's) path are exactly zero -- and nothing else in Gd / hd is written.  The rows->* and pairs->* tables are DEVICE
+ * tables and are not inspected by the call: the caller guarantees 0 <= frame, frame2 < n_frames, axis in 0..3,
+ * sphere_joint < nj, pair_sphere < n_spheres.  rows may be NULL (or rows->n_rows = 0) when pairs is given.  Enqueued on the
+ * handle's current compute stream, asynchronous.
+ *
+ * Refused, having touched nothing: PINKHIP_E_INVALID for a NULL handle / model, a NULL table or pointer, row0 < 0, strides
+ * smaller than the rows (sH < row0 + rows, sG < (row0 + rows) nv), dt that is not positive and finite, no rows at all,
+ * pairs->n_rows outside [1, n_pairs]; PINKHIP_E_UNSUPPORTED for nj > 64 (one lane per joint), more than 32 spheres or 64
+ * pairs, more than PINKHIP_MAX_MD rows.  B = 0 is fine. */
+#define PINKHIP_HAS_BARRIER_ROWS 1
+typedef struct pinkhip_barrier_rows {
+  int32_t n_rows;                       /* position + spherical rows described by the tables below */
+  const int32_t *frame, *axis, *frame2; /* [n_rows] device; frame slots of `model`; axis 3 = spherical; frame2 -1 otherwise */
+  const double *sign, *bound, *gain;    /* [n_rows] device */
+} pinkhip_barrier_rows;
+int pinkhip_barrier_rows_device(pinkhip_handle *h, const pinkhip_model *model, int64_t B, const double *q, double dt,
+                                const pinkhip_barrier_rows *rows, const pinkhip_sphere_pairs *pairs /* or NULL */,
+                                double *Gd, int64_t sG, double *hd, int64_t sH, int32_t row0,
+                                double *dist_out /* [B, pairs->n_rows] or NULL */);
+
 /* q [B,nq], q_target [nq] or [B,nq] -> lb, ub [B,nv]; posture error written into e [B,K] at columns
  * e_off .. e_off + nv - root_nv (e may be NULL) */
 int pinkhip_limits_posture_device(pinkhip_handle *h, const pinkhip_model *model, int64_t B, double dt,

@@ -135,6 +135,15 @@ class SpherePairsArgs(ctypes.Structure):
     ]
 
 
+class BarrierRowsArgs(ctypes.Structure):
+    """``pinkhip_barrier_rows``: device tables of the position / spherical barrier rows of ``pinkhip_barrier_rows_device``."""
+
+    _fields_ = [
+        ("n_rows", ctypes.c_int32), ("frame", ctypes.c_void_p), ("axis", ctypes.c_void_p), ("frame2", ctypes.c_void_p),
+        ("sign", ctypes.c_void_p), ("bound", ctypes.c_void_p), ("gain", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/pinkhip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
     "pinkhip_version", "pinkhip_device_count", "pinkhip_create", "pinkhip_destroy",
@@ -145,7 +154,7 @@ ABI_SYMBOLS = (
     "pinkhip_limits_posture_device", "pinkhip_check_limits_device", "pinkhip_integrate_device", "pinkhip_integrate_checked_device",
     "pinkhip_pose_targets_device", "pinkhip_solve_warm_device", "pinkhip_rollout_step_warm_device",
     "pinkhip_rollout_step_pairs_device", "pinkhip_com_create", "pinkhip_com_destroy", "pinkhip_com_task_device",
-    "pinkhip_manipulability_task_device", "pinkhip_rolling_tasks_device",
+    "pinkhip_manipulability_task_device", "pinkhip_rolling_tasks_device", "pinkhip_barrier_rows_device",
     "pinkhip_comm_get_unique_id", "pinkhip_comm_init", "pinkhip_comm_gather", "pinkhip_comm_gather_bytes",
     "pinkhip_comm_allgather_bytes", "pinkhip_comm_destroy",
     "pinkhip_host_alloc", "pinkhip_host_free", "pinkhip_malloc", "pinkhip_free",
@@ -201,6 +210,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.pinkhip_manipulability_task_device.argtypes = [vp, vp, i64, vp, i32, i32, i32, f64, vp, i64, vp, i64, i32, vp]
     if hasattr(lib, "pinkhip_rolling_tasks_device"):  # (PINKHIP_HAS_ROLLING_TASK: a library without it serves the host route)
         lib.pinkhip_rolling_tasks_device.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, vp, i64, vp, i64, i32, vp]
+    if hasattr(lib, "pinkhip_barrier_rows_device"):  # (PINKHIP_HAS_BARRIER_ROWS: a library without it evaluates barriers on the host)
+        lib.pinkhip_barrier_rows_device.argtypes = [vp, vp, i64, vp, f64, ctypes.POINTER(BarrierRowsArgs), ctypes.POINTER(SpherePairsArgs),
+                                                    vp, i64, vp, i64, i32, vp]
     lib.pinkhip_limits_posture_device.argtypes = [vp, vp, i64, f64, f64, vp, vp, i32, vp, vp, vp, i32, i32]
     lib.pinkhip_check_limits_device.argtypes = [vp, vp, i64, vp, ctypes.c_double, ctypes.POINTER(ctypes.c_int64)]
     lib.pinkhip_integrate_device.argtypes = [vp, vp, i64, vp, vp]

@@ -122,6 +122,8 @@ class BatchSolver:
             self.manipulability_task = self._manipulability_task
         if hasattr(self._lib, "pinkhip_rolling_tasks_device"):  # (PINKHIP_HAS_ROLLING_TASK)
             self.rolling_tasks = self._rolling_tasks
+        if hasattr(self._lib, "pinkhip_barrier_rows_device"):  # (PINKHIP_HAS_BARRIER_ROWS)
+            self.barrier_rows = self._barrier_rows
 
     @staticmethod
     def sharded(device_ids, solver_factory=None):
@@ -461,6 +463,19 @@ class BatchSolver:
         r = np.ascontiguousarray(radii, dtype=np.float64)
         self._check(self._lib.pinkhip_rolling_tasks_device(self._h, ctypes.c_void_p(model), B, q, n, s.ctypes.data, k.ctypes.data,
                                                            r.ctypes.data, e, sE, J, sJ, int(row0), height_out))
+
+    def _barrier_rows(self, model: int, B: int, q: int, dt: float, rows, pairs, Gd: int, sG: int, hd: int, sH: int, row0: int,
+                      dist_out=None) -> None:
+        """The barrier rows of every instance into ``Gd`` / ``hd`` from row ``row0`` on (``pinkhip_barrier_rows_device``), in
+        the form the solve consumes (``-J_h / dt``, ``gain alpha(h)``): ``rows`` -- a :class:`pink_amd._lib.BarrierRowsArgs`
+        of device tables, or ``None`` -- describes the PositionBarrier / BodySphericalBarrier rows (frame slots of the device
+        model), ``pairs`` -- a :class:`pink_amd._lib.SpherePairsArgs`, or ``None`` -- the sphere-pair rows behind them;
+        ``dist_out [B, pairs.n_rows]`` receives the selected distances.  Bound to the solver as ``barrier_rows`` only when the
+        loaded library has the symbol: ``hasattr(solver, "barrier_rows")`` is how the routes ask (a library without it
+        evaluates barriers on the host)."""
+        self._check(self._lib.pinkhip_barrier_rows_device(self._h, ctypes.c_void_p(model), B, q, float(dt),
+                                                          None if rows is None else ctypes.byref(rows),
+                                                          None if pairs is None else ctypes.byref(pairs), Gd, sG, hd, sH, int(row0), dist_out))
 
     def step_kernel(self, model: int, B: int, args) -> None:
         """Whole control step around the solve in one launch (``pinkhip_step_device``)."""

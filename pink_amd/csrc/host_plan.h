@@ -13,6 +13,7 @@
 
 #include "dispatch.h"
 #include "host_tables.h"
+#include "ik_barrier_rows.h"
 #include "ik_rollout.h"
 
 namespace pinkhip {
@@ -308,9 +309,9 @@ inline int plan_rollout(const pinkhip_desc &d, const ModelDev &md, bool has_rela
   return plan_rollout_step(d, md, has_relative, st, warm, nullptr, solver_env, ra, p, err);
 }
 
-// What pinkhip_rollout_step_pairs_device refuses about its sphere pairs `sp` before anything else is looked at (0: nothing):
-// the limits of the on-chip stage, and rows that are not the last barrier group of the descriptor's dense rows
-inline int pairs_fault(const pinkhip_desc &d, const pinkhip_sphere_pairs *sp, std::string &err) {
+// What every call that takes sphere pairs refuses about the tables of `sp` themselves (0: nothing): the limits of the on-chip
+// stage (pair_rows of ik_rollout.h, the sphere-pair stage of ik_barrier_rows.h)
+inline int pairs_tables_fault(const pinkhip_sphere_pairs *sp, std::string &err) {
   if (!sp) return refuse(err, PINKHIP_E_INVALID, "null sphere pairs");
   if (sp->n_spheres < 1 || sp->n_pairs < 1) return refuse(err, PINKHIP_E_INVALID, "sphere pairs need at least one sphere and one pair");
   if (sp->n_spheres > kPairsMaxSpheres) return refuse(err, PINKHIP_E_UNSUPPORTED, "more than 32 spheres");
@@ -319,8 +320,64 @@ inline int pairs_fault(const pinkhip_desc &d, const pinkhip_sphere_pairs *sp, st
   if (!sp->sphere_joint || !sp->sphere_centre || !sp->sphere_radius || !sp->column_mask || !sp->pair_sphere)
     return refuse(err, PINKHIP_E_INVALID, "sphere pairs: null table");
   if (!(sp->d_min >= 0.0) || !(sp->gain == sp->gain)) return refuse(err, PINKHIP_E_INVALID, "sphere pairs: bad d_min / gain");
+  return PINKHIP_OK;
+}
+
+// What pinkhip_rollout_step_pairs_device refuses about its sphere pairs `sp` before anything else is looked at (0: nothing):
+// the limits of the on-chip stage, and rows that are not the last barrier group of the descriptor's dense rows
+inline int pairs_fault(const pinkhip_desc &d, const pinkhip_sphere_pairs *sp, std::string &err) {
+  if (const int rc = pairs_tables_fault(sp, err)) return rc;
   if (d.n_barriers < 1 || !d.barrier_rows || d.barrier_rows[d.n_barriers] != d.md || d.barrier_rows[d.n_barriers - 1] != d.md - sp->n_rows)
     return refuse(err, PINKHIP_E_INVALID, "the sphere-pair rows must be the last barrier group of the dense rows (barrier_rows)");
+  return PINKHIP_OK;
+}
+
+inline void fill_pairs(const pinkhip_sphere_pairs &sp, PairsArgs &p) {
+  p.n_spheres = sp.n_spheres;
+  p.n_pairs = sp.n_pairs;
+  p.n_rows = sp.n_rows;
+  p.sphere_joint = sp.sphere_joint;
+  p.sphere_centre = sp.sphere_centre;
+  p.sphere_radius = sp.sphere_radius;
+  p.column_mask = sp.column_mask;
+  p.pair_sphere = sp.pair_sphere;
+  p.d_min = sp.d_min;
+  p.gain = sp.gain;
+}
+
+// pinkhip_barrier_rows_device: what it refuses before anything is enqueued (0: nothing, `a` filled), for the library and
+// the emulator alike
+inline int plan_barrier_rows(const ModelDev &md, long long B, const double *q, double dt, const pinkhip_barrier_rows *rows,
+                             const pinkhip_sphere_pairs *pairs, double *Gd, long long sG, double *hd, long long sH, int row0,
+                             double *dist_out, BarrierRowsArgs &a, std::string &err) {
+  if (B < 0 || B > 0x7fffffffLL) return refuse(err, PINKHIP_E_INVALID, "bad B");
+  if (row0 < 0) return refuse(err, PINKHIP_E_INVALID, "row0 must not be negative");
+  if (!(dt > 0.0) || !std::isfinite(dt)) return refuse(err, PINKHIP_E_INVALID, "dt must be positive and finite");
+  const int n = rows ? rows->n_rows : 0;
+  if (n < 0) return refuse(err, PINKHIP_E_INVALID, "negative number of rows");
+  if (n == 0 && !pairs) return refuse(err, PINKHIP_E_INVALID, "no rows at all");
+  if (n > 0 && (!rows->frame || !rows->axis || !rows->frame2 || !rows->sign || !rows->bound || !rows->gain))
+    return refuse(err, PINKHIP_E_INVALID, "barrier rows: null table");
+  if (pairs)
+    if (const int rc = pairs_tables_fault(pairs, err)) return rc;
+  const long long total = (long long)n + (pairs ? pairs->n_rows : 0);
+  if (total > PINKHIP_MAX_MD) return refuse(err, PINKHIP_E_UNSUPPORTED, "more than PINKHIP_MAX_MD barrier rows in one call");
+  if (md.nj > 64) return refuse(err, PINKHIP_E_UNSUPPORTED, "barrier rows need nj <= 64 (one lane per joint)");
+  a = BarrierRowsArgs{};
+  a.m = md;
+  a.B = B;
+  a.q = q;
+  a.dt = dt;
+  a.n_rows = n;
+  if (n > 0) {
+    a.frame = rows->frame, a.axis = rows->axis, a.frame2 = rows->frame2;
+    a.sign = rows->sign, a.bound = rows->bound, a.gain = rows->gain;
+  }
+  if (pairs) fill_pairs(*pairs, a.p);
+  a.Gd = Gd, a.hd = hd, a.sG = sG, a.sH = sH, a.row0 = row0, a.dist_out = dist_out;
+  if (B == 0) return PINKHIP_OK;
+  if (!q || !Gd || !hd) return refuse(err, PINKHIP_E_INVALID, "null pointer");
+  if (sH < row0 + total || sG < (row0 + total) * md.nv) return refuse(err, PINKHIP_E_INVALID, "strides smaller than the rows");
   return PINKHIP_OK;
 }
 
@@ -330,16 +387,7 @@ inline int plan_rollout_pairs(const pinkhip_desc &d, const ModelDev &md, bool ha
                               const pinkhip_sphere_pairs *sp, const char *solver_env, RolloutPairsArgs &pa, LaunchPlan &p, std::string &err) {
   p = LaunchPlan{};
   if (const int rc = pairs_fault(d, sp, err)) return rc;
-  pa.p.n_spheres = sp->n_spheres;
-  pa.p.n_pairs = sp->n_pairs;
-  pa.p.n_rows = sp->n_rows;
-  pa.p.sphere_joint = sp->sphere_joint;
-  pa.p.sphere_centre = sp->sphere_centre;
-  pa.p.sphere_radius = sp->sphere_radius;
-  pa.p.column_mask = sp->column_mask;
-  pa.p.pair_sphere = sp->pair_sphere;
-  pa.p.d_min = sp->d_min;
-  pa.p.gain = sp->gain;
+  fill_pairs(*sp, pa.p);
   return plan_rollout_step(d, md, has_relative, st, nullptr, sp, solver_env, pa.r, p, err);
 }
 

@@ -24,6 +24,7 @@
 #include "ik_manip.h"
 #include "ik_rolling.h"
 #include "ik_rollout.h"
+#include "ik_barrier_rows.h"
 #include "host_tables.h"
 #include "model_tables.h"
 #include "host_plan.h"
@@ -754,6 +755,21 @@ int pinkhip_rolling_tasks_device(pinkhip_handle *h, const pinkhip_model *m, int6
   if (B == 0) return PINKHIP_OK;
   PH_HIP(h, hipSetDevice(h->device));
   launch_grouped(h->stream, pinkhip::rolling_group_width(m->dev.nj), pinkhip::pose_lds_doubles(m->dev.nj), B, PH_WIDTHS(ik_rolling_tasks_kernel), a);
+  PH_HIP(h, hipGetLastError());
+  return PINKHIP_OK;
+}
+
+int pinkhip_barrier_rows_device(pinkhip_handle *h, const pinkhip_model *m, int64_t B, const double *q, double dt,
+                                const pinkhip_barrier_rows *rows, const pinkhip_sphere_pairs *pairs, double *Gd, int64_t sG,
+                                double *hd, int64_t sH, int32_t row0, double *dist_out) {
+  if (!h || !m) return fail(h, PINKHIP_E_INVALID, "null handle / model");
+  pinkhip::BarrierRowsArgs a;
+  std::string why;
+  if (const int rc = pinkhip::plan_barrier_rows(m->dev, B, q, dt, rows, pairs, Gd, sG, hd, sH, row0, dist_out, a, why)) return fail(h, rc, why);
+  if (B == 0) return PINKHIP_OK;
+  PH_HIP(h, hipSetDevice(h->device));
+  launch_grouped(h->stream, pinkhip::barrier_rows_group_width(m->dev.nj), pinkhip::barrier_rows_lds_doubles(m->dev.nj, a.p), B,
+                 PH_WIDTHS(ik_barrier_rows_kernel), a);
   PH_HIP(h, hipGetLastError());
   return PINKHIP_OK;
 }

@@ -9,7 +9,8 @@ identity-Jacobian ones (PostureTask, DampingTask, LowAccelerationTask, JointVelo
 the targets: ``pinkhip_fk_frame_tasks_device`` writes the rows straight into the packed ``J`` / ``e`` streams in HBM
 (``pink/tasks/frame_task.py:176-227``), the host only evaluates what is cheap and irregular -- the errors of the
 diagonal tasks, the limits (any list: explicit gains, AccelerationLimit, user subclasses), barriers -- and
-``pinkhip_solve_device`` stacks and solves.  ``J`` never exists on the host and never crosses PCIe.
+``pinkhip_solve_device`` stacks and solves.  ``J`` never exists on the host and never crosses PCIe.  Barriers the device forms (:func:`device_barriers`) do not reach the
+host either: ``pinkhip_barrier_rows_device`` writes their rows into ``Gd`` / ``hd`` behind the equality and limit rows.
 """
 
 from __future__ import annotations
@@ -117,6 +118,33 @@ def wheel_tables(tasks) -> tuple:
             [float(t.wheel_radius) for t in tasks])
 
 
+def device_barriers(model, barriers, api) -> Optional[list]:
+    """The barriers of a call in the order their rows take on the device -- Pink's, the SelfCollisionBarrier last -- when
+    ``pinkhip_barrier_rows_device`` forms ALL of them: the barriers the whole-step kernel forms
+    (:func:`pink_amd.solve_ik._barriers_declined`: PositionBarriers with the identity class-K function, BodySphericalBarriers,
+    at most one SelfCollisionBarrier of sphere pairs with one gain, none with a safe displacement of its own) on frames of the
+    model, a solver that has the call, at most 64 joints and ``PINKHIP_MAX_MD`` rows.  Else ``None``: the host evaluates
+    every barrier, as before."""
+    from .solve_ik import _barriers_declined
+
+    barriers = list(barriers or ())
+    if not barriers or not hasattr(api, "barrier_rows") or len(getattr(model, "joints", ())) > 64:
+        return None
+    if _barriers_declined(model, barriers, api, "barrier_rows") is not None:
+        return None
+    names = {fr.name for fr in getattr(model, "frames", ())}
+    if any(f not in names for bar in barriers if not hasattr(bar, "distance_query")
+           for f in (tuple(bar.frames) if hasattr(bar, "frames") else (bar.frame,))):
+        return None  # (an unknown frame: the host evaluation raises what it raises)
+    if sum(int(bar.dim) for bar in barriers) > MAX_BARRIER_ROWS:
+        return None
+    sc = [bar for bar in barriers if hasattr(bar, "distance_query")]
+    return [bar for bar in barriers if bar not in sc] + sc
+
+
+MAX_BARRIER_ROWS = 64  # include/pinkhip.h: PINKHIP_MAX_MD
+
+
 class HybridState:
     """Device buffers and model tables of one call shape (kept by :func:`pink_amd.solve_ik.solve_ik_batch` like the
     device-resident states)."""
@@ -132,6 +160,8 @@ class HybridState:
         self.dcom, self.com_key = None, None  # device copy of the model's mass tables (a ComTask slot)
         self.mframes, self.marrays, self.mmodel = None, None, None  # device model of the ManipulabilityTask slots' frames
         self.rframes, self.rarrays, self.rmodel = None, None, None  # device model of the wheels' (hub, floor) slots
+        self.bframes, self.barrays, self.bmodel = None, None, None  # device model of the barriers' frames
+        self.barrier_rows = None  # where the last call's barrier rows were formed: "device" / "host" / None (no barriers)
 
     def com_tables(self) -> int:
         """The device mass tables of the model as it is NOW (an edit of a mass or a centre builds them anew)."""
@@ -175,6 +205,39 @@ class HybridState:
         frame = hub, root = floor."""
         return self._frames_model("r", frames)
 
+    def barrier_model(self, frames) -> int:
+        """Device model whose frame slots are the frames of the PositionBarriers / BodySphericalBarriers."""
+        return self._frames_model("b", frames)
+
+    def barrier_tables(self, bars, dt: float):
+        """``(model, rows, pairs, sizes, safe gains)`` of ``pinkhip_barrier_rows_device`` for the barriers ``bars``
+        (:func:`device_barriers`): the device model of their frames, the ``pinkhip_barrier_rows`` / ``pinkhip_sphere_pairs``
+        structs on device tables (either may be ``None``), rows and safe-displacement gain per barrier."""
+        from ._lib import BarrierRowsArgs
+        from .rollout import barrier_row_tables, sphere_pair_tables, sphere_pairs_args
+
+        sc = next((bar for bar in bars if hasattr(bar, "distance_query")), None)
+        frames = []
+        for bar in bars:
+            for f in (() if bar is sc else tuple(bar.frames) if hasattr(bar, "frames") else (bar.frame,)):
+                if f not in frames:
+                    frames.append(f)
+        tables, sizes, bsafe = barrier_row_tables(bars, lambda name, what: frames.index(name), sc)
+        model = self.barrier_model(frames) if frames else self.dmodel  # (sphere pairs alone ride on joints: any model of the robot)
+        up = lambda name, a: (self.api.put(self.buf(name, a.nbytes), a), self.bufs[name][0])[1]  # noqa: E731
+        rows = None
+        if tables[0]:
+            rows = BarrierRowsArgs()
+            rows.n_rows = len(tables[0])
+            rows.frame, rows.axis, rows.sign, rows.bound, rows.gain, rows.frame2 = (
+                up("bar%d" % i, np.ascontiguousarray(v, dtype=t))
+                for i, (v, t) in enumerate(zip(tables, (np.int32, np.int32, np.float64, np.float64, np.float64, np.int32))))
+        pairs = None
+        if sc is not None:
+            host = sphere_pair_tables(self.model, sc.distance_query.pairs)
+            pairs = sphere_pairs_args([up("pairs%d" % i, a) for i, a in enumerate(host)], host, sc)
+        return model, rows, pairs, sizes, bsafe
+
     def constraint_model(self, frames) -> int:
         return self._frames_model("c", frames)
 
@@ -197,6 +260,7 @@ class HybridState:
             self.dcom = None
         self._destroy_frames_model("m")
         self._destroy_frames_model("r")
+        self._destroy_frames_model("b")
         self.api.model_destroy(self.dmodel)
 
 
@@ -229,7 +293,10 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
         rows = be.limit_rows(kq, limit, dt, lb, ub)
         if rows is not None:
             dense_rows.append(rows)
-    barrier_terms = [be.barrier_term(kq, bar) for bar in (barriers or [])]
+    # barriers: all of them by pinkhip_barrier_rows_device (below; the host only reserves their rows), or all of them here
+    dbars = device_barriers(model, barriers, api)
+    barrier_terms = [] if dbars is not None else [be.barrier_term(kq, bar) for bar in (barriers or [])]
+    state.barrier_rows = "device" if dbars is not None else ("host" if barriers else None)
     # equality constraints made of frame tasks (pink/solve_ik.py:125-149: A = J, b = -gain e): their rows are the leading
     # dense rows of the QP; the device writes them there (below), the host only reserves the space
     ccols = list(constraints or ())
@@ -285,12 +352,17 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     task_col0 = i32([0] * (nf + nc + nm + nw) + list(b0.task_col0))
     gain = f64([col[0].gain for col in fcols] + list(b0.gain))
     lm = f64([col[0].lm_damping for col in fcols] + list(b0.lm_damping))
+    md, n_bar = b0.md, int(b0.barrier_safe_gain.size)
     brow, bsafe = i32(b0.barrier_rows), f64(b0.barrier_safe_gain if b0.barrier_safe_gain.size else [0.0])
+    if dbars is not None:  # their rows behind the equality and limit rows b0 holds, one group per barrier
+        bmodel, brows, bpairs, sizes, safe = state.barrier_tables(dbars, dt)
+        brow, bsafe, n_bar = i32([b0.md + int(r) for r in np.cumsum([0] + sizes)]), f64(safe), len(dbars)
+        md = b0.md + int(sum(sizes))
     d = Desc()
-    d.B, d.nv, d.T, d.Kd, d.K, d.md, d.n_eq = B, nv, nf + nc + nm + nw + len(diag), Kd, K, b0.md, n_eq
+    d.B, d.nv, d.T, d.Kd, d.K, d.md, d.n_eq = B, nv, nf + nc + nm + nw + len(diag), Kd, K, md, n_eq
     d.task_rows, d.task_kind, d.task_col0 = (a.ctypes.data_as(c_int32_p) for a in (task_rows, task_kind, task_col0))
     d.gain, d.lm_damping = gain.ctypes.data_as(c_double_p), lm.ctypes.data_as(c_double_p)
-    d.n_barriers = int(b0.barrier_safe_gain.size)
+    d.n_barriers = n_bar
     d.barrier_rows, d.barrier_safe_gain = brow.ctypes.data_as(c_int32_p), bsafe.ctypes.data_as(c_double_p)
     d.damping, d.dt, d.cost_is_batched, d.max_iter = float(damping), float(dt), int(batched), int(max_iter)
     # device side
@@ -308,10 +380,16 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     p = Problem()
     p.J, p.e, p.cost, p.lb, p.ub = d_J, d_e, d_cost, d_lb, d_ub
     p.Gd = p.hd = p.c_extra = None
-    if b0.md:
-        p.Gd, p.hd = s.buf("Gd", b0.Gd.nbytes), s.buf("hd", b0.hd.nbytes)
-        api.put(p.Gd, b0.Gd)
-        api.put(p.hd, b0.hd)
+    if md:
+        p.Gd, p.hd = s.buf("Gd", 8 * B * md * nv), s.buf("hd", 8 * B * md)
+        if md == b0.md:
+            api.put(p.Gd, b0.Gd)
+            api.put(p.hd, b0.hd)
+        elif b0.md:  # (equality / limit rows in front of rows the device forms: one upload at the pitch of all rows)
+            Gd, hd = np.zeros((B, md, nv)), np.zeros((B, md))
+            Gd[:, :b0.md], hd[:, :b0.md] = b0.Gd, b0.hd
+            api.put(p.Gd, Gd)
+            api.put(p.hd, hd)
     if b0.c_extra is not None:
         p.c_extra = s.buf("c_extra", b0.c_extra.nbytes)
         api.put(p.c_extra, b0.c_extra)
@@ -336,13 +414,15 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
         ctargets = np.ascontiguousarray(np.stack([_targets_of(col, B) for col in ccols], axis=1))
         d_Tc = s.buf("Ttc", ctargets.nbytes)
         api.put(d_Tc, ctargets)
-        api.fk_frame_tasks(cmodel, B, d_q, d_Tc, None, p.hd, b0.md, p.Gd, b0.md * nv)
+        api.fk_frame_tasks(cmodel, B, d_q, d_Tc, None, p.hd, md, p.Gd, md * nv)
         api.sync()
-        hd = np.empty((B, b0.md))
+        hd = np.empty((B, md))
         api.get(hd, p.hd)
         for k, col in enumerate(ccols):
             hd[:, 6 * k:6 * k + 6] *= -float(col[0].gain)
         api.put(p.hd, hd)
+    if dbars is not None:  # ONE launch: the rows of every barrier behind the equality and limit rows
+        api.barrier_rows(bmodel, B, d_q, dt, brows, bpairs, p.Gd, md * nv, p.hd, md, b0.md)
     r = Result()
     r.dq, r.status, r.iters = d_dq, d_st, d_it
     api.solve_raw(d, p, r)

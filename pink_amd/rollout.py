@@ -78,6 +78,51 @@ def sphere_pair_tables(model: Model, pairs: Sequence[tuple]):
             np.ascontiguousarray(radii, dtype=np.float64), mask, np.ascontiguousarray(pair_sphere, dtype=np.int32).reshape(-1, 2))
 
 
+def barrier_row_tables(barriers: Sequence, slot_of, sc=None):
+    """Tables of the barrier rows the device forms (``include/pinkhip.h``: the ``barrier_*`` tables of ``pinkhip_rollout_step``,
+    ``pinkhip_barrier_rows``) for ``barriers`` in Pink's order: ``((frame, axis, sign, bound, gain, frame2), sizes, safe_gains)``
+    -- six lists with one entry per row, and per barrier its number of rows and its safe-displacement gain.  One dense row per
+    (index, side) of a PositionBarrier (``pink/barriers/position_barrier.py``: p_min rows, then p_max rows), one row of axis 3
+    and bound ``d_min^2`` per BodySphericalBarrier (class-K function ``h / (1 + |h|)``); ``slot_of(frame name, what)`` is the
+    frame's slot of the device model.  ``sc``: the SelfCollisionBarrier of sphere pairs among them -- its ``dim`` rows are
+    selected and formed on chip and have no entry in the lists."""
+    bf, ba, bs, bb, bg, bf2, sizes, bsafe = [], [], [], [], [], [], [], []
+    for bar in barriers:
+        bsafe.append(float(bar.safe_displacement_gain))
+        if sc is not None and bar is sc:
+            sizes.append(int(bar.dim))
+            continue
+        if hasattr(bar, "frames"):  # BodySphericalBarrier
+            f1, f2 = (slot_of(n, "spherical barrier") for n in bar.frames)
+            bf.append(f1), bf2.append(f2), ba.append(3), bs.append(1.0), bb.append(float(bar.d_min) ** 2)
+            bg.append(float(np.asarray(bar.gain, dtype=float).ravel()[0]))
+            sizes.append(1)
+            continue
+        if not getattr(bar, "identity_gain_function", False):
+            raise ValueError("position barriers on the device use the identity class-K function (the default)")
+        f = slot_of(bar.frame, "position barrier")
+        gains = np.asarray(bar.gain, dtype=float)
+        k = 0
+        for sign, bound in ((1.0, bar.p_min), (-1.0, bar.p_max)):
+            if bound is None:
+                continue
+            for i, idx in enumerate(bar.indices):
+                bf.append(f), bf2.append(f), ba.append(int(idx)), bs.append(sign), bb.append(float(np.asarray(bound)[i])), bg.append(float(gains[k]))
+                k += 1
+        sizes.append(k)
+    return (bf, ba, bs, bb, bg, bf2), sizes, bsafe
+
+
+def sphere_pairs_args(d_tables, tables, bar) -> "SpherePairsArgs":
+    """``pinkhip_sphere_pairs`` of the SelfCollisionBarrier ``bar`` whose tables (:func:`sphere_pair_tables`) live on the device
+    at ``d_tables``."""
+    sp = SpherePairsArgs()
+    sp.sphere_joint, sp.sphere_centre, sp.sphere_radius, sp.column_mask, sp.pair_sphere = d_tables
+    sp.n_spheres, sp.n_pairs, sp.n_rows = len(tables[0]), len(tables[4]), int(bar.dim)
+    sp.d_min, sp.gain = float(bar.d_min), float(np.asarray(bar.gain, dtype=float).ravel()[0])
+    return sp
+
+
 class ModelDesc(ctypes.Structure):
     """``pinkhip_model_desc``."""
 
@@ -229,8 +274,11 @@ class DeviceRollout:
         whole-step kernel (``fused="kernel"``).  ``position_barriers`` takes PositionBarriers and BodySphericalBarriers
         (``pink/barriers/body_spherical_barrier.py:73-143``) in Pink's order; their frames are slots of ``frame_tasks``
         (zero costs for a frame that carries no task) -- and at most ONE SelfCollisionBarrier whose ``distance_query`` is a
-        ``SpherePairs`` (``fused="kernel"`` only): its rows, selected and formed on chip per robot and step, are moved to
-        the end of the row groups (the order of the groups does not change the minimiser).  ``constraint_slots``: equality constraints made of frame tasks,
+        ``SpherePairs``: its rows, selected and formed on chip per robot and step, are moved to
+        the end of the row groups (the order of the groups does not change the minimiser).  The whole-step kernel
+        (``fused="kernel"``) forms all of these rows itself; with ``fused=True`` / ``fused=False`` ``pinkhip_barrier_rows_device``
+        forms them behind the other row kernels, in front of the solve, which then carries ``md`` dense rows (this is how
+        barriers go with a ComTask, ManipulabilityTasks or wheel tasks).  ``constraint_slots``: equality constraints made of frame tasks,
         ``(slot, gain)`` each (``pink/solve_ik.py:125-149``: ``A = J``, ``b = -gain e`` of the FrameTask of that slot of
         ``frame_tasks``, whose costs are zero when it is a constraint only); at most two.  The tables are the same for every robot and stay what they are over
         :meth:`run`: state that follows the previous step of each robot (``LowAccelerationTask.set_last_integration``,
@@ -365,7 +413,8 @@ class DeviceRollout:
                            np.ascontiguousarray(const_tasks[0][2]), np.ascontiguousarray(np.hstack([b for _, b, *_ in const_tasks])))
         self._extra_tasks = bool(const_tasks or diag_tasks)
         # position barriers (pink/barriers/position_barrier.py): one dense row per (index, side), rows in Pink's order
-        # (p_min rows, then p_max rows); formed on chip by the whole-step kernel (fused="kernel" only)
+        # (p_min rows, then p_max rows); formed on chip by the whole-step kernel (fused="kernel"), or by
+        # pinkhip_barrier_rows_device in front of the solve (fused=True / False)
         # FloatingBaseVelocityLimit (pink/limits/floating_base_velocity_limit.py:104-148): the Jacobian of a frame attached
         # to the root joint, on the root's tangent coordinates, is the constant adjoint of the frame's placement -- its
         # axis-aligned rows become a box on those coordinates, the others the first dense rows (constant too)
@@ -407,35 +456,18 @@ class DeviceRollout:
         if sc:
             self._pairs_host = self._sphere_pairs(model, sc)
             position_barriers = [bar for bar in position_barriers if bar is not sc[0]] + sc
-        bf, ba, bs, bb, bg, bf2, brow, bsafe = [], [], [], [], [], [], [n_eq + n_lim], []
-        for bar in position_barriers:
-            if bar is (sc[0] if sc else None):
-                brow.append(brow[-1] + int(bar.dim))
-                bsafe.append(float(bar.safe_displacement_gain))
-                continue
-            if hasattr(bar, "frames"):  # BodySphericalBarrier: one row, axis 3, bound d_min^2 (class-K function h / (1 + |h|))
-                f1, f2 = (plain_slot(n, "spherical barrier") for n in bar.frames)
-                bf.append(f1), bf2.append(f2), ba.append(3), bs.append(1.0), bb.append(float(bar.d_min) ** 2)
-                bg.append(float(np.asarray(bar.gain, dtype=float).ravel()[0]))
-                brow.append(n_eq + n_lim + len(bf))
-                bsafe.append(float(bar.safe_displacement_gain))
-                continue
-            if not getattr(bar, "identity_gain_function", False):
-                raise ValueError("position barriers on the device use the identity class-K function (the default)")
-            f = plain_slot(bar.frame, "position barrier")
-            gains = np.asarray(bar.gain, dtype=float)
-            k = 0
-            for sign, bound in ((1.0, bar.p_min), (-1.0, bar.p_max)):
-                if bound is None:
-                    continue
-                for i, idx in enumerate(bar.indices):
-                    bf.append(f), bf2.append(f), ba.append(int(idx)), bs.append(sign), bb.append(float(np.asarray(bound)[i])), bg.append(float(gains[k]))
-                    k += 1
-            brow.append(n_eq + n_lim + len(bf))
-            bsafe.append(float(bar.safe_displacement_gain))
+        (bf, ba, bs, bb, bg, bf2), sizes, bsafe = barrier_row_tables(position_barriers, plain_slot, sc[0] if sc else None)
+        brow = [n_eq + n_lim + int(r) for r in np.cumsum([0] + sizes)]
         self.md = n_eq + n_lim + len(bf) + (int(sc[0].dim) if sc else 0)
-        if self.md and self.fused != "kernel":
-            raise ValueError('position barriers and dense floating-base limit rows need the whole-step kernel: fused="kernel"')
+        # the whole-step kernel forms every kind of dense row; beside the step kernel + solve (fused=True) and the separate
+        # launches (fused=False) pinkhip_barrier_rows_device forms the barrier rows, in front of the solve -- the constant
+        # limit rows and the equality rows have no kernel there
+        if n_lim and self.fused != "kernel":
+            raise ValueError('dense floating-base limit rows need the whole-step kernel: fused="kernel"')
+        if self.md and self.fused != "kernel" and not hasattr(api, "barrier_rows"):
+            raise ValueError('this solver has no pinkhip_barrier_rows_device: position barriers need it, or the whole-step kernel (fused="kernel")')
+        if self.md and self.fused != "kernel" and len(model.joints) > 64:
+            raise ValueError("barrier rows on the device need a model of at most 64 joints")
         self.brow = np.ascontiguousarray(brow, dtype=np.int32)
         self.bsafe = np.ascontiguousarray(bsafe if bsafe else [0.0], dtype=np.float64)
         self._bar_host = [np.ascontiguousarray(v if v else [0], dtype=t) for v, t in
@@ -512,11 +544,7 @@ class DeviceRollout:
                 ptr = a.alloc(max(arr.nbytes, 8))
                 a.put(ptr, arr)
                 self.d_pairs.append(ptr)
-            sp = SpherePairsArgs()
-            sp.sphere_joint, sp.sphere_centre, sp.sphere_radius, sp.column_mask, sp.pair_sphere = self.d_pairs
-            sp.n_spheres, sp.n_pairs, sp.n_rows = len(self._pairs_host[0]), len(self._pairs_host[4]), int(sc[0].dim)
-            sp.d_min, sp.gain = float(sc[0].d_min), float(np.asarray(sc[0].gain, dtype=float).ravel()[0])
-            self._pairs = sp
+            self._pairs = sphere_pairs_args(self.d_pairs, self._pairs_host, sc[0])
         self.d_cons = []
         if self.cons:
             for arr in (np.ascontiguousarray([s_ for s_, _ in self.cons], dtype=np.int32), np.ascontiguousarray([g_ for _, g_ in self.cons], dtype=np.float64)):
@@ -538,6 +566,17 @@ class DeviceRollout:
         p = Problem()
         p.J, p.e, p.cost, p.lb, p.ub = self.d_J, self.d_e, self.d_cost, self.d_lb, self.d_ub
         p.Gd, p.hd, p.c_extra = None, None, None
+        self.d_Gd, self.d_hd, self._bar_rows = None, None, None
+        if self.md and self.fused != "kernel":  # the dense rows of the solve: written by _barrier_rows in front of it
+            from ._lib import BarrierRowsArgs
+
+            self.d_Gd, self.d_hd = f8(B, self.md, nv), f8(B, self.md)
+            p.Gd, p.hd = self.d_Gd, self.d_hd
+            if self._n_bar_rows:
+                br = BarrierRowsArgs()
+                br.n_rows = self._n_bar_rows
+                br.frame, br.axis, br.sign, br.bound, br.gain, br.frame2 = self.d_bar
+                self._bar_rows = br
         self.problem = p
         r = Result()
         r.dq, r.status, r.iters = self.d_dq, self.d_status, self.d_iters
@@ -590,8 +629,8 @@ class DeviceRollout:
         bar = sc[0]
         if len(sc) > 1:
             raise ValueError("at most one SelfCollisionBarrier per rollout")
-        if self.fused != "kernel" or not hasattr(self.api, "rollout_step_pairs"):
-            raise ValueError('a SelfCollisionBarrier needs the whole-step kernel (fused="kernel") of a solver with rollout_step_pairs')
+        if not hasattr(self.api, "rollout_step_pairs" if self.fused == "kernel" else "barrier_rows"):
+            raise ValueError('a SelfCollisionBarrier needs a solver with rollout_step_pairs (fused="kernel") or barrier_rows (fused=True / False)')
         if not isinstance(bar.distance_query, SpherePairs):
             raise ValueError("a SelfCollisionBarrier on the device needs a SpherePairs distance query")
         gains = np.asarray(bar.gain, dtype=float).ravel()
@@ -718,6 +757,12 @@ class DeviceRollout:
                                          self.d_e, self.K, self.d_J, self.Kd * self.nv, row0 + i,
                                          self.d_manip + 8 * self.B * i if m_out else None)
 
+    def _barrier_rows(self) -> None:
+        """The barrier rows of the configurations in ``d_q`` into the dense rows of the solve (``pinkhip_barrier_rows_device``):
+        position and spherical rows on the frame slots of the device model, then the sphere-pair rows."""
+        self.api.barrier_rows(self.dmodel, self.B, self.d_q, self.dt, self._bar_rows, self._pairs, self.d_Gd, self.md * self.nv,
+                              self.d_hd, self.md, 0)
+
     def _wheel_rows(self, heights: bool = False) -> None:
         """The RollingTask / OmniwheelTask rows of the configurations in ``d_q``, behind the frame, centre-of-mass and
         manipulability rows: one launch for all wheels."""
@@ -802,6 +847,8 @@ class DeviceRollout:
                 self._manip_rows()
             if self.wheel_tasks:
                 self._wheel_rows()
+            if self.d_Gd is not None:
+                self._barrier_rows()
             a.solve_raw(self.desc, self.problem, self.result)
             self._pending = bool(integrate)
         else:  # one launch for FK, one per FrameTask, limits + posture, solve, integrate
@@ -818,6 +865,8 @@ class DeviceRollout:
                 self._manip_rows()
             if self.wheel_tasks:
                 self._wheel_rows()
+            if self.d_Gd is not None:
+                self._barrier_rows()
             a.solve_raw(self.desc, self.problem, self.result)
             if integrate:
                 a.integrate_checked(self.dmodel, B, self.d_q, self.d_dq, self.d_status, self.d_fail, self.steps_done)
@@ -1126,7 +1175,7 @@ class DeviceRollout:
         if getattr(self, "rmodel", None) is not None:
             self.api.model_destroy(self.rmodel)
             self.rmodel = None
-        for name in ("d_com", "d_com_target", "d_manip", "d_heights"):
+        for name in ("d_com", "d_com_target", "d_manip", "d_heights", "d_Gd", "d_hd"):
             if getattr(self, name, None) is not None:
                 self.api.release(getattr(self, name))
                 setattr(self, name, None)

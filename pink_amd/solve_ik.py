@@ -415,8 +415,9 @@ def _spec_of(task):
     return (name, tuple(float(v) for v in task.cost[0:3]), tuple(float(v) for v in task.cost[3:6]), float(task.gain), float(task.lm_damping))
 
 
-def _self_collision_declined(model, bar, others: int, api) -> Optional[str]:
-    """Why the whole-step kernel does not form the rows of SelfCollisionBarrier ``bar`` (``None``: it does): one such barrier
+def _self_collision_declined(model, bar, others: int, api, call: str = "rollout_step_pairs") -> Optional[str]:
+    """Why the device kernels do not form the rows of SelfCollisionBarrier ``bar`` (``None``: they do; ``call``: the solver
+    method that forms them -- the whole-step kernel's, or ``"barrier_rows"`` of the stand-alone row kernel): one such barrier
     per call, a :class:`~pink_amd.barriers.self_collision_barrier.SpherePairs` query, one gain for all rows,
     ``1 <= n_collision_pairs <= len(pairs)`` (fewer pairs than rows is the host's ``InvalidCollisionPairs`` to raise), at
     most 32 distinct spheres and 64 pairs (``include/pinkhip.h``, ``pinkhip_sphere_pairs``), a solver that has the call."""
@@ -441,8 +442,35 @@ def _self_collision_declined(model, bar, others: int, api) -> Optional[str]:
     spheres = {(j, c.tobytes(), r) for j1, c1, r1, j2, c2, r2 in query.pairs for j, c, r in ((j1, c1, r1), (j2, c2, r2))}
     if len(spheres) > MAX_SPHERES:
         return f"SelfCollisionBarrier with {len(spheres)} distinct spheres (the whole-step kernel holds {MAX_SPHERES})"
-    if api is None or not hasattr(api() if callable(api) else api, "rollout_step_pairs"):
-        return "SelfCollisionBarrier: this solver has no rollout_step_pairs"
+    if api is None or not hasattr(api() if callable(api) else api, call):
+        return f"SelfCollisionBarrier: this solver has no {call}"
+    return None
+
+
+def _barriers_declined(model, barriers, api, call: str = "rollout_step_pairs") -> Optional[str]:
+    """Why the device kernels do not form the rows of ``barriers`` (``None``: they form all of them) -- the whole-step kernel
+    (:func:`_device_kinematics_plan`) and the stand-alone barrier-row kernel of the hybrid route (:mod:`pink_amd.hybrid`) take
+    the same ones: PositionBarriers with the default class-K function, BodySphericalBarriers with one gain and at most one
+    SelfCollisionBarrier of sphere pairs (:func:`_self_collision_declined`), none with a safe displacement of its own."""
+    from .barriers.barrier import Barrier
+    from .barriers.body_spherical_barrier import BodySphericalBarrier
+    from .barriers.position_barrier import PositionBarrier
+    from .barriers.self_collision_barrier import SelfCollisionBarrier
+
+    n_sc = 0
+    for bar in barriers or ():
+        if type(bar).compute_safe_displacement is not Barrier.compute_safe_displacement:
+            return f"{type(bar).__name__} with a safe displacement of its own"
+        if type(bar) is PositionBarrier:
+            if not bar.identity_gain_function:
+                return "PositionBarrier with a class-K function of its own"
+        elif type(bar) is SelfCollisionBarrier:
+            why = _self_collision_declined(model, bar, n_sc, api, call)
+            if why is not None:
+                return why
+            n_sc += 1
+        elif type(bar) is not BodySphericalBarrier or np.ndim(bar.gain) > 1 or np.size(bar.gain) != 1:
+            return f"barrier {type(bar).__name__}: only PositionBarrier, BodySphericalBarrier and sphere-pair SelfCollisionBarrier rows are formed on chip"
     return None
 
 
@@ -457,8 +485,6 @@ def _device_kinematics_plan(configurations, tasks, limits, barriers, constraints
     -- else ``None``.  Frames that only a barrier or a constraint needs become slots of the device model with ZERO cost
     (``pink/tasks/task.py:148-166``: nothing enters the objective for them); ``constraints`` is a tuple of
     ``(slot, gain)``."""
-    from .barriers.barrier import Barrier
-    from .barriers.body_spherical_barrier import BodySphericalBarrier
     from .barriers.position_barrier import PositionBarrier
     from .barriers.self_collision_barrier import SelfCollisionBarrier
     from .tasks.frame_task import FrameTask
@@ -467,27 +493,16 @@ def _device_kinematics_plan(configurations, tasks, limits, barriers, constraints
     B = len(configurations)
     if B == 0:
         return None
-    n_sc = 0
     model = configurations.model if hasattr(configurations, "model") else configurations[0].model
     lim = _default_limits_gain(model, limits)
     if lim is None:
         return _declined("limits other than one ConfigurationLimit + at most one VelocityLimit / AccelerationLimit / FloatingBaseVelocityLimit of this model")
     gain, acc, vmax = lim
-    for bar in barriers or ():
-        # position barriers with the default class-K function and spherical barriers, neither with a safe displacement of
-        # its own, are formed on chip
-        if type(bar).compute_safe_displacement is not Barrier.compute_safe_displacement:
-            return _declined(f"{type(bar).__name__} with a safe displacement of its own")
-        if type(bar) is PositionBarrier:
-            if not bar.identity_gain_function:
-                return _declined("PositionBarrier with a class-K function of its own")
-        elif type(bar) is SelfCollisionBarrier:
-            why = _self_collision_declined(model, bar, n_sc, api)
-            if why is not None:
-                return _declined(why)
-            n_sc += 1
-        elif type(bar) is not BodySphericalBarrier or np.ndim(bar.gain) > 1 or np.size(bar.gain) != 1:
-            return _declined(f"barrier {type(bar).__name__}: only PositionBarrier, BodySphericalBarrier and sphere-pair SelfCollisionBarrier rows are formed on chip")
+    # position barriers with the default class-K function and spherical barriers, neither with a safe displacement of
+    # its own, are formed on chip
+    why = _barriers_declined(model, barriers, api)
+    if why is not None:
+        return _declined(why)
     flat = [t for entry in (tasks or ()) for t in (entry if isinstance(entry, (list, tuple)) else (entry,))]
     from .tasks.manipulability_task import ManipulabilityTask
 
@@ -1021,7 +1036,7 @@ def solve_ik_batch(configurations: Sequence, tasks: Sequence, dt: float, solver:
             plan = _declined("no instantiation of the whole-step kernel holds this model's rows")
         else:
             result = BatchResult(dq, status, iters, path)
-            _record_stats(result, "device")
+            _record_stats(result, "device", "device" if barriers else None)
             _report_route("device", len(configurations), tasks, limits, barriers, constraints, strict_route)
             if status.any():
                 raise NoSolutionFound(None, result, result.failed_indices(), status[status != 0])
@@ -1052,7 +1067,7 @@ def solve_ik_batch(configurations: Sequence, tasks: Sequence, dt: float, solver:
             and hasattr(api, "fk_frame_tasks") and hasattr(api, "solve_raw")):
         result = _solve_hybrid(configurations, tasks, dt, damping, limits, barriers, constraints, api, max_iter) if strict_route in (None, "hybrid") else None
         if result is not None:
-            _record_stats(result, "hybrid")
+            _record_stats(result, "hybrid", getattr(result, "barrier_rows", None))
             _report_route("hybrid", B, tasks, limits, barriers, constraints, strict_route, warn=not rows_only)
             if not result.all_found:
                 raise NoSolutionFound(None, result, result.failed_indices(), result.status[result.status != 0])
@@ -1061,7 +1076,7 @@ def solve_ik_batch(configurations: Sequence, tasks: Sequence, dt: float, solver:
     batch = pack_configurations(configurations, tasks, dt, damping, limits, barriers, pool[0] if pool else solver_handle,
                                 gpu_frame_tasks=bool(kwargs.get("gpu_frame_tasks", True)), constraints=constraints)
     result = api.solve(batch, max_iter=max_iter)
-    _record_stats(result, "host-evaluated")
+    _record_stats(result, "host-evaluated", "host" if barriers else None)
     if not result.all_found:
         raise NoSolutionFound(batch, result, result.failed_indices(), result.status[result.status != 0])
     return np.divide(result.dq, dt, out=out) if out is not None else result.dq / dt
@@ -1116,7 +1131,9 @@ def _solve_hybrid(configurations, tasks, dt, damping, limits, barriers, constrai
     cache[key] = state
     while len(cache) > _ROLLOUT_CACHE_MAX:
         cache.pop(next(iter(cache))).free()
-    return BatchResult(dq, status, iters, path)
+    result = BatchResult(dq, status, iters, path)
+    result.barrier_rows = state.barrier_rows  # (where this call's barrier rows were formed: last_solve_stats)
+    return result
 
 
 def pinned_empty(shape, dtype=np.float64, solver_handle=None) -> np.ndarray:
@@ -1132,18 +1149,20 @@ def pinned_empty(shape, dtype=np.float64, solver_handle=None) -> np.ndarray:
 _LAST_STATS: dict = {}
 
 
-def _record_stats(result, route: str) -> None:
+def _record_stats(result, route: str, barrier_rows: Optional[str] = None) -> None:
     """Keeps the result of the call; the figures are worked out when :func:`last_solve_stats` asks for them (three passes
     over the batch: 0.2 ms of a 1.5 ms call at B = 65 536)."""
     _LAST_STATS.clear()
-    _LAST_STATS.update(route=route, _result=result)
+    _LAST_STATS.update(route=route, barrier_rows=barrier_rows, _result=result)
 
 
 def last_solve_stats() -> dict:
     """What the last :func:`solve_ik_batch` call of this process did: ``route`` (``"device"``: kinematics, rows and QP
     formed on the device from ``q``; ``"hybrid"``: FrameTask rows (and one ComTask's, up to four ManipulabilityTasks', up to eight RollingTasks' / OmniwheelTasks') formed on the device from ``q``, the other tasks /
     limits / barriers evaluated on the host, QP on the device; ``"host-evaluated"``: everything evaluated on the host,
-    QP on the device), ``instances``, ``failed``, ``iters_mean`` and ``paths`` -- the share of the batch per solver path
+    QP on the device), ``barrier_rows`` (where the rows of the call's barriers were formed: ``"device"`` -- by the whole-step kernel
+    on the device route, by ``pinkhip_barrier_rows_device`` on the hybrid route --, ``"host"``, or ``None`` for a call without
+    barriers), ``instances``, ``failed``, ``iters_mean`` and ``paths`` -- the share of the batch per solver path
     (:meth:`pink_amd.batch_solver.BatchResult.path_fractions`; ``handover`` is the share that paid for both solvers)."""
     result = _LAST_STATS.pop("_result", None)
     if result is not None:
