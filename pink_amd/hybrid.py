@@ -15,7 +15,6 @@ host either: ``pinkhip_barrier_rows_device`` writes their rows into ``Gd`` / ``h
 
 from __future__ import annotations
 
-import ctypes
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -25,24 +24,22 @@ from ._lib import Desc, Problem, Result, c_double_p, c_int32_p
 from .batch import DiagonalTaskTerm, pack_terms
 from .batch_solver import split_iters
 from .exceptions import PinkError
+from .row_groups import (KINDS, MAX_BARRIER_ROWS, MAX_MANIPULABILITY_TASKS, MAX_WHEELS, BarrierRows, Layout, ManipulabilityGroup,  # noqa: F401
+                         WheelGroup, barrier_frames, barrier_rows_declined, declined, wheel_tables)  # (the limits and wheel_tables: re-exported)
 
 MAX_FRAME_TASKS = 16
-MAX_MANIPULABILITY_TASKS = 4
-MAX_WHEELS = 8  # include/pinkhip.h: PINKHIP_MAX_WHEELS
 
 
-def plan(kin_model, slots: Sequence, constraints) -> Optional[List[int]]:
+def plan(kin_model, slots: Sequence, constraints, api=None) -> Optional[List[int]]:
     """Indices of the FrameTask slots when the hybrid route serves this stack, else ``None``: at least one FrameTask,
-    at most one ComTask on a model that carries mass (two or more: the host evaluates them), at most four
-    ManipulabilityTask slots (each with one frame, mask, reference frame and rate for the whole batch), at most eight
-    RollingTask / OmniwheelTask slots (each with one class, hub, floor, radius, gain, cost and lm_damping for the whole batch),
-    every other task of a
-    class whose batched evaluator yields a diagonal term; equality constraints (slots of ``constraints=``) made of
-    FrameTasks / RelativeFrameTasks."""
-    from .tasks.com_task import ComTask
+    the slots of every kind of :data:`pink_amd.row_groups.KINDS` admitted by that kind on the solver ``api`` (at most one
+    ComTask on a model that carries mass -- two or more: the host evaluates them --, at most four ManipulabilityTask slots,
+    each with one frame, mask, reference frame and rate for the whole batch, at most eight RollingTask / OmniwheelTask
+    slots, each with one class, hub, floor, radius, gain, cost and lm_damping for the whole batch), every other task of a class
+    whose batched evaluator yields a diagonal term; equality constraints (slots of ``constraints=``) made of FrameTasks /
+    RelativeFrameTasks."""
     from .tasks.frame_task import FrameTask
     from .tasks.linear_holonomic_task import JointVelocityTask
-    from .tasks.manipulability_task import ManipulabilityTask
     from .tasks.posture_task import DampingTask, LowAccelerationTask, PostureTask
     from .tasks.relative_frame_task import RelativeFrameTask
 
@@ -67,55 +64,25 @@ def plan(kin_model, slots: Sequence, constraints) -> Optional[List[int]]:
             return None
     if not frames or len(frames) > MAX_FRAME_TASKS:
         return None
-    coms = [k for k, col in enumerate(slots) if type(col[0]) is ComTask]
-    if len(coms) > 1 or (coms and not (kin_model.total_mass > 0.0 and len(kin_model.joints) <= 64)):
-        return None
-    manips = manipulability_slots(slots)
-    if len(manips) > MAX_MANIPULABILITY_TASKS or (manips and len(kin_model.joints) > 64):
+    coms, manips, wheels = kslots = group_slots(slots)
+    if declined(kin_model, [[slots[k][0] for k in ks] for ks in kslots], api) is not None:
         return None
     for k in manips:  # (a per-instance list that differs in frame / mask / reference frame / rate / gain / cost: the host route, as frame slots)
-        if any(type(t) is not ManipulabilityTask for t in slots[k]) or not be.manipulability_slot_is_uniform(slots[k], with_weights=True):
+        if any(type(t) not in ManipulabilityGroup.types for t in slots[k]) or not be.manipulability_slot_is_uniform(slots[k], with_weights=True):
             return None
-    wheels = rolling_slots(slots)
-    if len(wheels) > MAX_WHEELS or (wheels and len(kin_model.joints) > 64):
-        return None
     for k in wheels:  # (a per-instance list that differs in class / hub / floor / radius / gain / cost: the host route)
         if not be.rolling_slot_is_uniform(slots[k], with_weights=True):
             return None
-    for k, col in enumerate(slots):
-        if k not in frames and k not in coms and k not in manips and k not in wheels and type(col[0]) not in (PostureTask, DampingTask, LowAccelerationTask, JointVelocityTask):
-            return None
+    dense = set(frames).union(*kslots)
+    if any(k not in dense and type(col[0]) not in (PostureTask, DampingTask, LowAccelerationTask, JointVelocityTask) for k, col in enumerate(slots)):
+        return None
     return frames
 
 
-def com_slot(slots: Sequence) -> Optional[int]:
-    """Index of the ComTask slot of a stack :func:`plan` accepted, or ``None``."""
-    from .tasks.com_task import ComTask
-
-    return next((k for k, col in enumerate(slots) if type(col[0]) is ComTask), None)
-
-
-def manipulability_slots(slots: Sequence) -> List[int]:
-    """Indices of the ManipulabilityTask slots of a stack, in stack order."""
-    from .tasks.manipulability_task import ManipulabilityTask
-
-    return [k for k, col in enumerate(slots) if type(col[0]) is ManipulabilityTask]
-
-
-def rolling_slots(slots: Sequence) -> List[int]:
-    """Indices of the RollingTask / OmniwheelTask slots of a stack, in stack order."""
-    from .tasks.rolling_task import OmniwheelTask, RollingTask
-
-    return [k for k, col in enumerate(slots) if type(col[0]) in (RollingTask, OmniwheelTask)]
-
-
-def wheel_tables(tasks) -> tuple:
-    """``(frames, kinds, radii)`` of the wheels ``tasks`` for ``pinkhip_rolling_tasks_device``: the ``(hub, floor)`` pairs that
-    become the relative slots of a device model, 0 (rolling) / 1 (omniwheel), and the radii."""
-    from .tasks.rolling_task import OmniwheelTask
-
-    return (tuple((t.hub_frame, t.floor_frame) for t in tasks), [1 if type(t) is OmniwheelTask else 0 for t in tasks],
-            [float(t.wheel_radius) for t in tasks])
+def group_slots(slots: Sequence) -> List[List[int]]:
+    """Per kind of :data:`pink_amd.row_groups.KINDS` -- ComTask, ManipulabilityTask, RollingTask / OmniwheelTask -- the indices
+    of its slots of a stack, in stack order."""
+    return [[k for k, col in enumerate(slots) if type(col[0]) in kind.types] for kind in KINDS]
 
 
 def device_barriers(model, barriers, api) -> Optional[list]:
@@ -128,21 +95,17 @@ def device_barriers(model, barriers, api) -> Optional[list]:
     from .solve_ik import _barriers_declined
 
     barriers = list(barriers or ())
-    if not barriers or not hasattr(api, "barrier_rows") or len(getattr(model, "joints", ())) > 64:
+    if not barriers or barrier_rows_declined(model, api) is not None:
         return None
     if _barriers_declined(model, barriers, api, "barrier_rows") is not None:
         return None
     names = {fr.name for fr in getattr(model, "frames", ())}
-    if any(f not in names for bar in barriers if not hasattr(bar, "distance_query")
-           for f in (tuple(bar.frames) if hasattr(bar, "frames") else (bar.frame,))):
+    if any(f not in names for f in barrier_frames(barriers)):
         return None  # (an unknown frame: the host evaluation raises what it raises)
     if sum(int(bar.dim) for bar in barriers) > MAX_BARRIER_ROWS:
         return None
     sc = [bar for bar in barriers if hasattr(bar, "distance_query")]
     return [bar for bar in barriers if bar not in sc] + sc
-
-
-MAX_BARRIER_ROWS = 64  # include/pinkhip.h: PINKHIP_MAX_MD
 
 
 class HybridState:
@@ -156,11 +119,10 @@ class HybridState:
         self.arrays = ModelArrays(model, list(frames))
         self.dmodel = api.model_create(self.arrays.desc)
         self.bufs = {}
-        self.cframes, self.carrays, self.cmodel = None, None, None  # device model of the equality constraints' frames
+        # further device models by name -- "constraints": the equality constraints' frames; the name of a row group
+        # (pink_amd/row_groups.py): the slots of its tasks; "barriers": the barriers' frames -- as (frames, arrays, handle)
+        self.models = {}
         self.dcom, self.com_key = None, None  # device copy of the model's mass tables (a ComTask slot)
-        self.mframes, self.marrays, self.mmodel = None, None, None  # device model of the ManipulabilityTask slots' frames
-        self.rframes, self.rarrays, self.rmodel = None, None, None  # device model of the wheels' (hub, floor) slots
-        self.bframes, self.barrays, self.bmodel = None, None, None  # device model of the barriers' frames
         self.barrier_rows = None  # where the last call's barrier rows were formed: "device" / "host" / None (no barriers)
 
     def com_tables(self) -> int:
@@ -175,71 +137,21 @@ class HybridState:
             self.com_key = key
         return self.dcom
 
-    def _frames_model(self, p: str, frames) -> int:
-        """Device model whose frame slots are ``frames``, behind the attributes ``<p>frames`` / ``<p>arrays`` / ``<p>model``;
-        built anew when the frames change."""
+    def _frames_model(self, name: str, frames) -> int:
+        """Device model ``name`` whose frame slots are ``frames`` (an entry ``(frame, root)``: a relative slot); built anew
+        when the frames change."""
         frames = tuple(frames)
-        if getattr(self, p + "frames") != frames:
+        if name not in self.models or self.models[name][0] != frames:
             from .rollout import ModelArrays
 
-            self._destroy_frames_model(p)
-            arrays = ModelArrays(self.model, list(frames))
-            setattr(self, p + "arrays", arrays)  # (kept: the descriptor points into its arrays)
-            setattr(self, p + "model", self.api.model_create(arrays.desc))
-            setattr(self, p + "frames", frames)
-        return getattr(self, p + "model")
+            self._destroy_frames_model(name)
+            arrays = ModelArrays(self.model, list(frames))  # (kept: the descriptor points into its arrays)
+            self.models[name] = (frames, arrays, self.api.model_create(arrays.desc))
+        return self.models[name][2]
 
-    def _destroy_frames_model(self, p: str) -> None:
-        if getattr(self, p + "model") is not None:
-            self.api.model_destroy(getattr(self, p + "model"))
-            setattr(self, p + "model", None)
-            setattr(self, p + "frames", None)
-
-    def manipulability_model(self, frames) -> int:
-        """Device model whose frame slots are the frames of the ManipulabilityTask slots (the frame-task model's slots each
-        own six rows of the frame kernel)."""
-        return self._frames_model("m", frames)
-
-    def rolling_model(self, frames) -> int:
-        """Device model whose slots are the ``(hub, floor)`` pairs of the RollingTask / OmniwheelTask slots: relative slots,
-        frame = hub, root = floor."""
-        return self._frames_model("r", frames)
-
-    def barrier_model(self, frames) -> int:
-        """Device model whose frame slots are the frames of the PositionBarriers / BodySphericalBarriers."""
-        return self._frames_model("b", frames)
-
-    def barrier_tables(self, bars, dt: float):
-        """``(model, rows, pairs, sizes, safe gains)`` of ``pinkhip_barrier_rows_device`` for the barriers ``bars``
-        (:func:`device_barriers`): the device model of their frames, the ``pinkhip_barrier_rows`` / ``pinkhip_sphere_pairs``
-        structs on device tables (either may be ``None``), rows and safe-displacement gain per barrier."""
-        from ._lib import BarrierRowsArgs
-        from .rollout import barrier_row_tables, sphere_pair_tables, sphere_pairs_args
-
-        sc = next((bar for bar in bars if hasattr(bar, "distance_query")), None)
-        frames = []
-        for bar in bars:
-            for f in (() if bar is sc else tuple(bar.frames) if hasattr(bar, "frames") else (bar.frame,)):
-                if f not in frames:
-                    frames.append(f)
-        tables, sizes, bsafe = barrier_row_tables(bars, lambda name, what: frames.index(name), sc)
-        model = self.barrier_model(frames) if frames else self.dmodel  # (sphere pairs alone ride on joints: any model of the robot)
-        up = lambda name, a: (self.api.put(self.buf(name, a.nbytes), a), self.bufs[name][0])[1]  # noqa: E731
-        rows = None
-        if tables[0]:
-            rows = BarrierRowsArgs()
-            rows.n_rows = len(tables[0])
-            rows.frame, rows.axis, rows.sign, rows.bound, rows.gain, rows.frame2 = (
-                up("bar%d" % i, np.ascontiguousarray(v, dtype=t))
-                for i, (v, t) in enumerate(zip(tables, (np.int32, np.int32, np.float64, np.float64, np.float64, np.int32))))
-        pairs = None
-        if sc is not None:
-            host = sphere_pair_tables(self.model, sc.distance_query.pairs)
-            pairs = sphere_pairs_args([up("pairs%d" % i, a) for i, a in enumerate(host)], host, sc)
-        return model, rows, pairs, sizes, bsafe
-
-    def constraint_model(self, frames) -> int:
-        return self._frames_model("c", frames)
+    def _destroy_frames_model(self, name: str) -> None:
+        if name in self.models:
+            self.api.model_destroy(self.models.pop(name)[2])
 
     def buf(self, name: str, nbytes: int) -> int:
         have = self.bufs.get(name)
@@ -250,17 +162,20 @@ class HybridState:
             self.bufs[name] = have
         return have[0]
 
+    def upload(self, name: str, a: np.ndarray) -> int:
+        """Device address of the buffer ``name`` after ``a`` went into it."""
+        self.api.put(self.buf(name, a.nbytes), a)
+        return self.bufs[name][0]
+
     def free(self) -> None:
         for ptr, _ in self.bufs.values():
             self.api.release(ptr)
         self.bufs = {}
-        self._destroy_frames_model("c")
+        for name in list(self.models):
+            self._destroy_frames_model(name)
         if self.dcom is not None:
             self.api.com_destroy(self.dcom)
             self.dcom = None
-        self._destroy_frames_model("m")
-        self._destroy_frames_model("r")
-        self._destroy_frames_model("b")
         self.api.model_destroy(self.dmodel)
 
 
@@ -273,17 +188,9 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     nv, nq, nf = model.nv, model.nq, len(frame_slots)
     kq = _QOnly(model, kin_q, kin)
     # diagonal tasks, limits, barriers: host (vectorised, pink_amd/batch_eval.py)
-    kc = com_slot(slots)
-    ccol = None if kc is None else slots[kc]
-    nc = 0 if ccol is None else 1
-    km = manipulability_slots(slots)
-    mcols = [slots[k] for k in km]
-    nm = len(mcols)
-    kr = rolling_slots(slots)
-    rcols = [slots[k] for k in kr]
-    rwidths = [len(col[0].rows) for col in rcols]
-    nr = sum(rwidths)
-    diag = [be.task_term(kq, col, None) for k, col in enumerate(slots) if k not in frame_slots and k != kc and k not in km and k not in kr]
+    kslots = group_slots(slots)
+    dense = set(frame_slots).union(*kslots)
+    diag = [be.task_term(kq, col, None) for k, col in enumerate(slots) if k not in dense]
     if any(not isinstance(t, DiagonalTaskTerm) for t in diag):
         raise PinkError("hybrid route: a task outside the FrameTasks produced a dense Jacobian")
     lb = np.full((B, nv), -np.inf)
@@ -304,69 +211,56 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
     eq = [(np.zeros((B, n_eq, nv)), np.zeros((B, n_eq)))] if n_eq else ()
     b0 = pack_terms(nv, diag, dt, damping, boxes=[(lb, ub)], dense_rows=dense_rows, barriers=barrier_terms, batch_size=B,
                     equality_rows=eq)
-    # the FrameTask part of the descriptor: one dense task of six rows per slot, in slot order
-    fcols = [slots[k] for k in frame_slots]
-    for col in fcols:  # (gain / lm_damping are read off the first task of a slot: the same refusal as the host route)
+
+    def weights(col, w, none=None):
+        # (gain / lm_damping are read off the first task of a slot: the same refusal as the host route)
         be._check_slot(col)
-    # ... and the ComTask's: one dense task of three rows behind them
-    if ccol is not None:
-        be._check_slot(ccol)
-        ctarget = np.ascontiguousarray(be.com_targets(ccol, B), dtype=np.float64)
-    # ... and one dense task of one row per ManipulabilityTask slot behind those
-    for col in mcols:
-        be._check_slot(col)
-    # ... and one dense task of three (Rolling) or two (Omniwheel) rows per wheel slot behind those
-    for col in rcols:
-        be._check_slot(col)
-    Kd = 6 * nf + 3 * nc + nm + nr
-    K = Kd + b0.K
-    fcost = [be._costs(col, 6) for col in fcols]
-    widths = [6] * nf + [3] * nc + [1] * nm + rwidths
-    if ccol is not None:
-        fcost.append(be._costs(ccol, 3))
-        fcols = fcols + [ccol]
-    for col in mcols:
-        fcost.append(be._costs(col, 1))
-        fcols = fcols + [col]
-    for col, w in zip(rcols, rwidths):
         c = be._costs(col, w)
-        fcost.append(1.0 if c is None else c)  # (cost=None: identity weights, pink/tasks/task.py:148-156)
-        fcols = fcols + [col]
-    batched = b0.cost.ndim == 2 or any(np.ndim(c) == 2 for c in fcost)
-    if batched:
-        cost = np.concatenate([np.broadcast_to(np.asarray(c, dtype=float), (B, w)) for c, w in zip(fcost, widths)]
-                              + [np.broadcast_to(b0.cost, (B, b0.K))], axis=1)
-    else:
-        cost = np.concatenate([np.broadcast_to(np.asarray(c, dtype=float), (w,)) for c, w in zip(fcost, widths)] + [b0.cost])
-    cost = np.ascontiguousarray(cost)
+        return col[0].gain, col[0].lm_damping, none if c is None else c
+
+    # the dense part of the descriptor: one task of six rows per FrameTask slot, in slot order, then the row groups -- three
+    # rows of the ComTask, one per ManipulabilityTask slot, three (Rolling) or two (Omniwheel) per wheel slot
+    fcols = [slots[k] for k in frame_slots]
+    frame_weights = [weights(col, 6) for col in fcols]
+    groups = []
+    for kind, ks in zip(KINDS, kslots):
+        cols = [slots[k] for k in ks]
+        # (cost=None of a wheel: identity weights, pink/tasks/task.py:148-156)
+        groups.append(kind([col[0] for col in cols], [weights(col, kind.width(col[0]), 1.0 if kind is WheelGroup else None) for col in cols]))
+    lay = Layout(frame_weights, groups)
+    com = groups[0]
+    if com.tasks:
+        ctarget = np.ascontiguousarray(be.com_targets(slots[kslots[0][0]], B), dtype=np.float64)
+    Kd, K = lay.Kd, lay.Kd + b0.K
+    batched = b0.cost.ndim == 2 or any(np.ndim(c) == 2 for c in lay.costs)
+    cost = np.ascontiguousarray(np.concatenate(lay.cost_segments((B,) if batched else ())
+                                               + [np.broadcast_to(b0.cost, (B, b0.K)) if batched else b0.cost], axis=-1))
     e_full = np.zeros((B, K))  # (the kernel overwrites the FrameTask rows: one contiguous upload instead of a strided one)
     e_full[:, Kd:] = b0.e
     # (a RelativeFrameTask's target lives in its root frame: a relative slot of the device model, include/pinkhip.h)
-    targets = np.ascontiguousarray(np.stack([_targets_of(col, B) for col in fcols[:nf]], axis=1))  # [B, nf, 12]
+    targets = np.ascontiguousarray(np.stack([_targets_of(col, B) for col in fcols], axis=1))  # [B, nf, 12]
     i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)  # noqa: E731
     f64 = lambda v: np.ascontiguousarray(v, dtype=np.float64)  # noqa: E731
-    nw = len(rcols)
-    task_rows = i32([6 * i for i in range(nf + 1)] + [6 * nf + 3] * nc + [6 * nf + 3 * nc + i + 1 for i in range(nm)]
-                    + [6 * nf + 3 * nc + nm + int(r) for r in np.cumsum(rwidths)] + [Kd + int(r) for r in b0.task_rows[1:]])
-    task_kind = i32([0] * (nf + nc + nm + nw) + list(b0.task_kind))
-    task_col0 = i32([0] * (nf + nc + nm + nw) + list(b0.task_col0))
-    gain = f64([col[0].gain for col in fcols] + list(b0.gain))
-    lm = f64([col[0].lm_damping for col in fcols] + list(b0.lm_damping))
-    md, n_bar = b0.md, int(b0.barrier_safe_gain.size)
+    task_rows = i32(lay.task_rows + [Kd + int(r) for r in b0.task_rows[1:]])
+    task_kind, task_col0 = i32(lay.task_kind + list(b0.task_kind)), i32(lay.task_col0 + list(b0.task_col0))
+    gain, lm = f64(lay.gain + list(b0.gain)), f64(lay.lm_damping + list(b0.lm_damping))
+    md, n_bar, s = b0.md, int(b0.barrier_safe_gain.size), state
     brow, bsafe = i32(b0.barrier_rows), f64(b0.barrier_safe_gain if b0.barrier_safe_gain.size else [0.0])
-    if dbars is not None:  # their rows behind the equality and limit rows b0 holds, one group per barrier
-        bmodel, brows, bpairs, sizes, safe = state.barrier_tables(dbars, dt)
-        brow, bsafe, n_bar = i32([b0.md + int(r) for r in np.cumsum([0] + sizes)]), f64(safe), len(dbars)
-        md = b0.md + int(sum(sizes))
+    if dbars is not None:  # their rows behind the equality and limit rows b0 holds, one group per barrier, on a device model
+        # of the barriers' own frames (sphere pairs alone ride on joints: any model of the robot)
+        frames = barrier_frames(dbars)
+        bar = BarrierRows(model, dbars, lambda name, what: frames.index(name))
+        bar.upload(s.upload, s._frames_model("barriers", frames) if frames else s.dmodel, b0.md)
+        brow, bsafe, n_bar = i32([b0.md + int(r) for r in np.cumsum([0] + bar.sizes)]), f64(bar.safe), len(dbars)
+        md = b0.md + int(sum(bar.sizes))
     d = Desc()
-    d.B, d.nv, d.T, d.Kd, d.K, d.md, d.n_eq = B, nv, nf + nc + nm + nw + len(diag), Kd, K, md, n_eq
+    d.B, d.nv, d.T, d.Kd, d.K, d.md, d.n_eq = B, nv, lay.n_tasks + len(diag), Kd, K, md, n_eq
     d.task_rows, d.task_kind, d.task_col0 = (a.ctypes.data_as(c_int32_p) for a in (task_rows, task_kind, task_col0))
     d.gain, d.lm_damping = gain.ctypes.data_as(c_double_p), lm.ctypes.data_as(c_double_p)
     d.n_barriers = n_bar
     d.barrier_rows, d.barrier_safe_gain = brow.ctypes.data_as(c_int32_p), bsafe.ctypes.data_as(c_double_p)
     d.damping, d.dt, d.cost_is_batched, d.max_iter = float(damping), float(dt), int(batched), int(max_iter)
     # device side
-    s = state
     d_q, d_Tt = s.buf("q", 8 * B * nq), s.buf("Tt", 8 * B * nf * 12)
     d_J, d_e, d_cost = s.buf("J", 8 * B * Kd * nv), s.buf("e", 8 * B * K), s.buf("cost", cost.nbytes)
     d_lb, d_ub = s.buf("lb", 8 * B * nv), s.buf("ub", 8 * B * nv)
@@ -394,26 +288,19 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
         p.c_extra = s.buf("c_extra", b0.c_extra.nbytes)
         api.put(p.c_extra, b0.c_extra)
     api.fk_frame_tasks(s.dmodel, B, d_q, d_Tt, None, d_e, K, d_J, Kd * nv)
-    if ccol is not None:  # the three ComTask rows behind the frame rows of the same streams
-        d_ct = s.buf("com_target", ctarget.nbytes)
-        api.put(d_ct, ctarget)
-        api.com_task(s.dmodel, s.com_tables(), B, d_q, d_ct, ctarget.ndim == 2, d_e, K, d_J, Kd * nv, 6 * nf)
-    if nm:  # one row per ManipulabilityTask slot behind the centre-of-mass rows, one launch each
-        mmodel = s.manipulability_model(col[0].frame for col in mcols)
-        for i, col in enumerate(mcols):
-            t0 = col[0]
-            api.manipulability_task(mmodel, B, d_q, i, int(t0.reference_frame), t0.row_mask, float(t0.manipulability_rate), d_e, K,
-                                    d_J, Kd * nv, 6 * nf + 3 * nc + i)
-    if nw:  # the rows of all wheels behind the manipulability rows, ONE launch: the world poses are composed once
-        frames, kinds, radii = wheel_tables([col[0] for col in rcols])
-        api.rolling_tasks(s.rolling_model(frames), B, d_q, list(range(nw)), kinds, radii, d_e, K, d_J, Kd * nv, 6 * nf + 3 * nc + nm)
+    # the rows of the groups behind the frame rows of the same streams; the state keeps their device models, and the mass
+    # tables as the model has them NOW
+    for g in lay.groups:
+        g.dmodel = s.dmodel if g.frames() is None else s._frames_model(g.name, g.frames())
+    if com.tasks:
+        com.dcom, com.d_target, com.batched = s.com_tables(), s.upload("com_target", ctarget), ctarget.ndim == 2
+    lay.launch_all(api, B, d_q, d_e, K, d_J, Kd * nv)
     if n_eq:
         # the same kernel on the constraints' frames, writing J into the leading rows of Gd and e into those of hd (row
         # pitches md nv and md); hd then becomes -gain e on the host: [B, md] doubles go home and back
-        cmodel = s.constraint_model(_frame_name(col[0]) for col in ccols)
+        cmodel = s._frames_model("constraints", (_frame_name(col[0]) for col in ccols))
         ctargets = np.ascontiguousarray(np.stack([_targets_of(col, B) for col in ccols], axis=1))
-        d_Tc = s.buf("Ttc", ctargets.nbytes)
-        api.put(d_Tc, ctargets)
+        d_Tc = s.upload("Ttc", ctargets)
         api.fk_frame_tasks(cmodel, B, d_q, d_Tc, None, p.hd, md, p.Gd, md * nv)
         api.sync()
         hd = np.empty((B, md))
@@ -422,7 +309,7 @@ def solve(state: HybridState, kin_q: np.ndarray, kin, slots: Sequence, frame_slo
             hd[:, 6 * k:6 * k + 6] *= -float(col[0].gain)
         api.put(p.hd, hd)
     if dbars is not None:  # ONE launch: the rows of every barrier behind the equality and limit rows
-        api.barrier_rows(bmodel, B, d_q, dt, brows, bpairs, p.Gd, md * nv, p.hd, md, b0.md)
+        bar.launch(api, B, d_q, dt, p.Gd, md * nv, p.hd, md)
     r = Result()
     r.dq, r.status, r.iters = d_dq, d_st, d_it
     api.solve_raw(d, p, r)

@@ -228,7 +228,7 @@ class DeviceRollout:
     """
 
     _BUFFERS = ("d_q", "d_T", "d_Jb", "d_Tt", "d_J", "d_e", "d_cost", "d_lb", "d_ub", "d_dq", "d_status", "d_iters", "d_qt",
-                "d_fail", "d_Tq")
+                "d_fail", "d_Tq", "d_acc", "d_active", "d_Gd", "d_hd")
 
     def __init__(self, api, model: Model, q0: np.ndarray, frame_tasks: Sequence[tuple], dt: float,
                  posture_cost: Optional[float] = None, posture_gain: float = 1.0, damping: float = 1e-12,
@@ -238,26 +238,20 @@ class DeviceRollout:
                  diag_tasks: Sequence = (), acceleration_limit: Optional[np.ndarray] = None,
                  velocity_limit: Optional[np.ndarray] = None, constraint_slots: Sequence = (), warm_start: bool = False,
                  com_task=None, manipulability_tasks: Sequence = (), rolling_tasks: Sequence = ()):
-        """``rolling_tasks``: up to eight :class:`pink_amd.tasks.RollingTask` / :class:`~pink_amd.tasks.OmniwheelTask`
-        (``pink/tasks/rolling_task.py``, ``omniwheel_task.py``) whose three / two rows each ``pinkhip_rolling_tasks_device`` forms
-        behind the FrameTask, ComTask and ManipulabilityTask rows, from the configuration the step solves at, all wheels in one
-        launch (``fused=True``: step kernel, rolling kernel, solve; ``fused=False``: one more launch in front of the solve).
-        The whole-step kernel does not form these rows: ``fused="kernel"`` raises.  :meth:`wheel_heights` returns the hubs'
-        heights over their floors.
-
-        ``manipulability_tasks``: up to four :class:`pink_amd.tasks.ManipulabilityTask` (``pink/tasks/manipulability_task.py``)
-        whose one row each ``pinkhip_manipulability_task_device`` forms behind the FrameTask and ComTask rows, from the
-        configuration the step solves at (``fused=True``: step kernel, one launch per task, solve; ``fused=False``: the same
-        launches in front of the solve).  The whole-step kernel does not form these rows: ``fused="kernel"`` raises.
-        :meth:`manipulability` returns the indices themselves.
-
-        ``com_task``: a :class:`pink_amd.tasks.ComTask` (``pink/tasks/com_task.py``) whose three rows
-        ``pinkhip_com_task_device`` forms behind the FrameTask rows, from the configuration the step solves at and the
-        model's mass tables (``fused=True``: step kernel, centre-of-mass kernel, solve; ``fused=False``: one more launch in
-        front of the solve).  The whole-step kernel does not form centre-of-mass rows: ``fused="kernel"`` raises.  The target
-        is the task's (one for all robots, or ``[B, 3]``) until :meth:`set_com_target` replaces it.  The model's mass tables
+        """``com_task``, ``manipulability_tasks``, ``rolling_tasks``: tasks whose rows stand-alone kernels form behind the
+        FrameTask rows, from the configuration the step solves at, in that order (:mod:`pink_amd.row_groups`; ``fused=True``:
+        step kernel, their launches, solve; ``fused=False``: the same launches in front of the solve).  The whole-step kernel
+        does not form these rows: ``fused="kernel"`` raises.
+        ``com_task``: a :class:`pink_amd.tasks.ComTask` (``pink/tasks/com_task.py``), three rows by
+        ``pinkhip_com_task_device`` from the model's mass tables; :meth:`center_of_mass` returns the centres themselves.  The
+        target is the task's (one for all robots, or ``[B, 3]``) until :meth:`set_com_target` replaces it.  The mass tables
         are copied to the device ONCE, here: an edit of ``Joint.mass`` / ``Joint.com`` afterwards is not seen by this rollout
         (build a new one; :func:`pink_amd.solve_ik_batch` on the hybrid route compares the tables with every call).
+        ``manipulability_tasks``: up to four :class:`pink_amd.tasks.ManipulabilityTask` (``pink/tasks/manipulability_task.py``),
+        one row and one launch of ``pinkhip_manipulability_task_device`` each; :meth:`manipulability` returns the indices.
+        ``rolling_tasks``: up to eight :class:`pink_amd.tasks.RollingTask` / :class:`~pink_amd.tasks.OmniwheelTask`
+        (``pink/tasks/rolling_task.py``, ``omniwheel_task.py``), three / two rows each, all wheels in one launch of
+        ``pinkhip_rolling_tasks_device``; :meth:`wheel_heights` returns the hubs' heights over their floors.
 
         ``warm_start``: every step starts its QP solver from the active set the previous step of the same robot ended
         on (the joints saturated at step t are mostly those saturated at step t + 1: fewer sweeps, fewer exchanges, the
@@ -295,44 +289,23 @@ class DeviceRollout:
                              'no equality constraints, no dense floating-base limit rows')
         self.B = B = int(q0.shape[0])
         self.nv, self.nq = model.nv, model.nq
-        self.com_task, self.dcom, self.d_com, self.d_com_target = com_task, None, None, None
-        if com_task is not None:
-            if self.fused == "kernel":
-                raise ValueError('the whole-step kernel does not form centre-of-mass rows: a ComTask needs fused=True or fused=False')
-            if not hasattr(api, "com_task"):
-                raise ValueError("this solver has no pinkhip_com_task_device: a ComTask needs it")
-            if not model.total_mass > 0.0:
-                raise ValueError("the model carries no mass: its centre of mass is undefined")
-            if len(model.joints) > 64:
-                raise ValueError("centre-of-mass rows on the device need a model of at most 64 joints")
-        self.manip_tasks, self.mmodel, self.d_manip = list(manipulability_tasks), None, None
-        if self.manip_tasks:
-            from .tasks.manipulability_task import ManipulabilityTask, check_revolute_path
+        # the dense rows stand-alone kernels form behind the FrameTask rows (pink_amd/row_groups.py): what each kind admits
+        from .row_groups import KINDS, BarrierRows, Layout, barrier_rows_declined, declined
 
-            if self.fused == "kernel":
-                raise ValueError('the whole-step kernel does not form manipulability rows: a ManipulabilityTask needs fused=True or fused=False')
-            if not hasattr(api, "manipulability_task"):
-                raise ValueError("this solver has no pinkhip_manipulability_task_device: a ManipulabilityTask needs it")
-            if len(self.manip_tasks) > 4 or any(type(t) is not ManipulabilityTask for t in self.manip_tasks):
-                raise ValueError("manipulability_tasks: at most four ManipulabilityTask objects")
-            if len(model.joints) > 64:
-                raise ValueError("manipulability rows on the device need a model of at most 64 joints")
-            for t in self.manip_tasks:
-                check_revolute_path(model, t.frame)
-        self.wheel_tasks, self.rmodel, self.d_heights = list(rolling_tasks), None, None
-        if self.wheel_tasks:
-            from .tasks.rolling_task import OmniwheelTask, RollingTask
+        def weights(t, none=None):
+            return float(t.gain), float(t.lm_damping), none if t.cost is None else t.cost
 
-            if self.fused == "kernel":
-                raise ValueError('the whole-step kernel does not form wheel-contact rows: a RollingTask / OmniwheelTask needs fused=True or fused=False')
-            if not hasattr(api, "rolling_tasks"):
-                raise ValueError("this solver has no pinkhip_rolling_tasks_device: a RollingTask / OmniwheelTask needs it")
-            if len(self.wheel_tasks) > 8 or any(type(t) not in (RollingTask, OmniwheelTask) for t in self.wheel_tasks):
-                raise ValueError("rolling_tasks: at most eight RollingTask / OmniwheelTask objects")
-            if len(model.joints) > 64:
-                raise ValueError("wheel-contact rows on the device need a model of at most 64 joints")
-            for t in self.wheel_tasks:  # (an unknown frame: what a FrameTask raises)
-                model.getFrameId(t.hub_frame), model.getFrameId(t.floor_frame)
+        self.com, self.manip, self.wheels = groups = [
+            kind(tasks, [weights(t, none) for t in tasks])
+            for kind, tasks, none in zip(KINDS, ([] if com_task is None else [com_task], manipulability_tasks, rolling_tasks), (None, 1.0, 1.0))]
+        for g in groups:
+            if g.tasks and self.fused == "kernel":
+                raise ValueError(f'the whole-step kernel does not form {g.rows}: {g.needs} needs fused=True or fused=False')
+        why = declined(model, [g.tasks for g in groups], api)
+        if why is not None:
+            raise ValueError(why)
+        for g in groups:
+            g.validate(model)
         # (a frame task (frame, ...) regulates the frame in the world; ((frame, root), ...) the pose of frame in root --
         # a RelativeFrameTask, pink/tasks/relative_frame_task.py: a relative slot of the device model)
         self.arrays = ModelArrays(model, [ft[0] for ft in frame_tasks], velocity_limit=velocity_limit)
@@ -359,31 +332,19 @@ class DeviceRollout:
             raise ValueError("constant-row tasks: A must be [k, nv] and q_0 [nq]")
         if self.n_crow and any(not np.array_equal(q_0, const_tasks[0][2]) for _, _, q_0, *_ in const_tasks):
             raise ValueError("constant-row tasks must share one reference configuration q_0")
-        self.n_com = 3 if com_task is not None else 0
-        self.n_manip = len(self.manip_tasks)
-        self.n_wheel_rows = sum(len(t.rows) for t in self.wheel_tasks)
-        self.Kd = 6 * nf + self.n_crow + self.n_com + self.n_manip + self.n_wheel_rows  # (n_crow = 0 beside these: constant-row tasks need fused="kernel")
+        # the frame rows, then the rows of the groups (constant-row tasks need fused="kernel", the groups refuse it: one or the other)
+        self.layout = lay = Layout([(ft[3], ft[4], np.hstack([np.broadcast_to(np.asarray(c, float), (3,)) for c in ft[1:3]]))
+                                    for ft in frame_tasks], groups)
+        self.Kd = lay.Kd + self.n_crow
         n_post = nv - root_nv if posture_cost is not None else 0
         self.K = self.Kd + n_post + sum(e.shape[0] for _, e, *_ in diag_tasks)
         # task tables of the QP (include/pinkhip.h: frame tasks, constant-row tasks, then the diagonal ones: the posture first)
-        rows, kind, col0, gain, lm, cost = [0], [], [], [], [], []
-        for ft in frame_tasks:
-            rows.append(rows[-1] + 6), kind.append(0), col0.append(0), gain.append(ft[3]), lm.append(ft[4])
-            cost += list(np.broadcast_to(np.asarray(ft[1], float), (3,))) + list(np.broadcast_to(np.asarray(ft[2], float), (3,)))
+        rows, kind, col0, gain, lm = (list(v) for v in (lay.task_rows, lay.task_kind, lay.task_col0, lay.gain, lay.lm_damping))
+        cost = [c for seg in lay.cost_segments() for c in seg]
         for A, b, _, c, g, l in const_tasks:
             k = A.shape[0]
             rows.append(rows[-1] + k), kind.append(0), col0.append(0), gain.append(g), lm.append(l)
             cost += list(np.broadcast_to(np.ones(k) if c is None else np.asarray(c, float), (k,)))
-        if com_task is not None:  # three dense rows behind the frame rows
-            rows.append(rows[-1] + 3), kind.append(0), col0.append(0), gain.append(float(com_task.gain)), lm.append(float(com_task.lm_damping))
-            cost += list(np.broadcast_to(np.asarray(com_task.cost, float), (3,)))
-        for t in self.manip_tasks:  # one dense row each behind the centre-of-mass rows
-            rows.append(rows[-1] + 1), kind.append(0), col0.append(0), gain.append(float(t.gain)), lm.append(float(t.lm_damping))
-            cost.append(float(1.0 if t.cost is None else t.cost))
-        for t in self.wheel_tasks:  # three or two dense rows each behind the manipulability rows
-            w = len(t.rows)
-            rows.append(rows[-1] + w), kind.append(0), col0.append(0), gain.append(float(t.gain)), lm.append(float(t.lm_damping))
-            cost += list(np.broadcast_to(np.asarray(1.0 if t.cost is None else t.cost, float), (w,)))
         if n_post:
             rows.append(rows[-1] + n_post), kind.append(1), col0.append(root_nv), gain.append(posture_gain), lm.append(posture_lm_damping)
             cost += [float(posture_cost)] * n_post
@@ -452,27 +413,20 @@ class DeviceRollout:
 
         # one SelfCollisionBarrier of sphere pairs: the last row group (include/pinkhip.h, pinkhip_sphere_pairs)
         sc = [bar for bar in position_barriers if hasattr(bar, "distance_query")]
-        self._pairs_host, self.d_pairs, self._pairs = None, [], None
         if sc:
-            self._pairs_host = self._sphere_pairs(model, sc)
             position_barriers = [bar for bar in position_barriers if bar is not sc[0]] + sc
-        (bf, ba, bs, bb, bg, bf2), sizes, bsafe = barrier_row_tables(position_barriers, plain_slot, sc[0] if sc else None)
-        brow = [n_eq + n_lim + int(r) for r in np.cumsum([0] + sizes)]
-        self.md = n_eq + n_lim + len(bf) + (int(sc[0].dim) if sc else 0)
+        self.bars = bars = BarrierRows(model, position_barriers, plain_slot, self._sphere_pairs(model, sc) if sc else None)
+        brow = [n_eq + n_lim + int(r) for r in np.cumsum([0] + bars.sizes)]
+        self.md = n_eq + n_lim + bars.n_rows + (int(sc[0].dim) if sc else 0)
         # the whole-step kernel forms every kind of dense row; beside the step kernel + solve (fused=True) and the separate
         # launches (fused=False) pinkhip_barrier_rows_device forms the barrier rows, in front of the solve -- the constant
         # limit rows and the equality rows have no kernel there
         if n_lim and self.fused != "kernel":
             raise ValueError('dense floating-base limit rows need the whole-step kernel: fused="kernel"')
-        if self.md and self.fused != "kernel" and not hasattr(api, "barrier_rows"):
-            raise ValueError('this solver has no pinkhip_barrier_rows_device: position barriers need it, or the whole-step kernel (fused="kernel")')
-        if self.md and self.fused != "kernel" and len(model.joints) > 64:
-            raise ValueError("barrier rows on the device need a model of at most 64 joints")
+        if self.md and self.fused != "kernel" and barrier_rows_declined(model, api) is not None:
+            raise ValueError(barrier_rows_declined(model, api))
         self.brow = np.ascontiguousarray(brow, dtype=np.int32)
-        self.bsafe = np.ascontiguousarray(bsafe if bsafe else [0.0], dtype=np.float64)
-        self._bar_host = [np.ascontiguousarray(v if v else [0], dtype=t) for v, t in
-                          ((bf, np.int32), (ba, np.int32), (bs, np.float64), (bb, np.float64), (bg, np.float64), (bf2, np.int32))]
-        self._n_bar_rows = len(bf)
+        self.bsafe = np.ascontiguousarray(bars.safe if bars.safe else [0.0], dtype=np.float64)
         d = Desc()
         d.B, d.nv, d.T, d.Kd, d.K, d.md, d.n_eq = B, nv, T, self.Kd, self.K, self.md, n_eq
         d.task_rows = self.task_rows.ctypes.data_as(c_int32_p)
@@ -503,54 +457,31 @@ class DeviceRollout:
         a.put(self.d_fail, np.zeros(B, dtype=np.int32))
         self._fail_dirty = False
         self.d_qt = f8(B, nq)
+        for g in lay.groups:  # (the mass tables, a device model of the group's own slots, its output buffer)
+            g.create(a, model, self.dmodel, B)
         if com_task is not None:
             from . import batch_eval as be
 
-            self.dcom = a.com_create(self.dmodel, *model.mass_tables())
-            self.d_com, self.d_com_target = f8(B, 3), f8(B, 3)
             self.set_com_target(be.com_targets([com_task], B))
-        if self.manip_tasks:  # (a device model of its own: every frame slot of dmodel owns six rows of the step kernel)
-            self.marrays = ModelArrays(model, [t.frame for t in self.manip_tasks])  # (kept: the descriptor points into its arrays)
-            self.mmodel = a.model_create(self.marrays.desc)
-            self.d_manip = f8(B, self.n_manip)
-        if self.wheel_tasks:  # (a device model of its own: its slots are the wheels' (hub, floor) pairs, relative slots)
-            from .hybrid import wheel_tables
-
-            frames, self.wheel_kinds, self.wheel_radii = wheel_tables(self.wheel_tasks)
-            self.rarrays = ModelArrays(model, list(frames))  # (kept: the descriptor points into its arrays)
-            self.rmodel = a.model_create(self.rarrays.desc)
-            self.d_heights = f8(B, len(self.wheel_tasks))
         if self.warm_start:  # one byte per robot and tangent coordinate, read and written in place by every step
             self.d_active = a.alloc(B * nv)
             a.put(self.d_active, np.zeros(B * nv, dtype=np.uint8))
-        self.d_bar, self.d_lim, self.d_extra = [], [], []
-        if self._extra_tasks:  # tables of the constant-row tasks and the batch-constant errors of the extra diagonal tasks
-            for arr in ([self._diag_e] + (list(self._const) if self._const else [])):
-                ptr = a.alloc(max(arr.nbytes, 8))
-                a.put(ptr, arr)
-                self.d_extra.append(ptr)
+
+        def up(name, arr):  # (a table on the device)
+            ptr = a.alloc(max(arr.nbytes, 8))
+            a.put(ptr, arr)
+            return ptr
+
+        # tables of the constant-row tasks and the batch-constant errors of the extra diagonal tasks
+        self.d_lim, self.d_extra = [], [up("extra", arr) for arr in [self._diag_e] + list(self._const or ())] if self._extra_tasks else []
         for arr in ([] if self.root_box is None else [self.root_box, np.ascontiguousarray(self.lim_rows), self.lim_h]):
             ptr = a.alloc(max(arr.nbytes, 8))
             if arr.nbytes:
                 a.put(ptr, arr)
             self.d_lim.append(ptr)
-        if self._n_bar_rows:
-            for arr in self._bar_host:
-                ptr = a.alloc(max(arr.nbytes, 8))
-                a.put(ptr, arr)
-                self.d_bar.append(ptr)
-        if self._pairs_host is not None:
-            for arr in self._pairs_host:
-                ptr = a.alloc(max(arr.nbytes, 8))
-                a.put(ptr, arr)
-                self.d_pairs.append(ptr)
-            self._pairs = sphere_pairs_args(self.d_pairs, self._pairs_host, sc[0])
-        self.d_cons = []
-        if self.cons:
-            for arr in (np.ascontiguousarray([s_ for s_, _ in self.cons], dtype=np.int32), np.ascontiguousarray([g_ for _, g_ in self.cons], dtype=np.float64)):
-                ptr = a.alloc(max(arr.nbytes, 8))
-                a.put(ptr, arr)
-                self.d_cons.append(ptr)
+        bars.upload(up, self.dmodel, 0)  # (on the frame slots of the rollout's own model, from dense row 0 on)
+        self.d_bar, self.d_pairs, self._pairs = bars.d_rows, bars.d_pairs, bars.pairs
+        self.d_cons = [up("cons", np.ascontiguousarray(v, dtype=t)) for v, t in zip(zip(*self.cons), (np.int32, np.float64))]
         self._resident = {}  # frame slot -> token of the frozen target array d_Tt holds for it (FrameTask.freeze_targets)
         self.qt_batched = 1  # d_qt holds [B, nq] (one posture target per robot) or [nq] (one for all)
         self.targets_per_frame = False  # d_Tt holds [B, nf, 12], or one [B, 12] array per frame
@@ -566,17 +497,10 @@ class DeviceRollout:
         p = Problem()
         p.J, p.e, p.cost, p.lb, p.ub = self.d_J, self.d_e, self.d_cost, self.d_lb, self.d_ub
         p.Gd, p.hd, p.c_extra = None, None, None
-        self.d_Gd, self.d_hd, self._bar_rows = None, None, None
-        if self.md and self.fused != "kernel":  # the dense rows of the solve: written by _barrier_rows in front of it
-            from ._lib import BarrierRowsArgs
-
+        self.d_Gd, self.d_hd = None, None
+        if self.md and self.fused != "kernel":  # the dense rows of the solve: written by the barrier kernel in front of it
             self.d_Gd, self.d_hd = f8(B, self.md, nv), f8(B, self.md)
             p.Gd, p.hd = self.d_Gd, self.d_hd
-            if self._n_bar_rows:
-                br = BarrierRowsArgs()
-                br.n_rows = self._n_bar_rows
-                br.frame, br.axis, br.sign, br.bound, br.gain, br.frame2 = self.d_bar
-                self._bar_rows = br
         self.problem = p
         r = Result()
         r.dq, r.status, r.iters = self.d_dq, self.d_status, self.d_iters
@@ -736,74 +660,43 @@ class DeviceRollout:
 
     def set_com_target(self, target) -> None:
         """Target of the ComTask from the next step on: ``[3]`` for every robot, or ``[B, 3]``."""
-        if self.com_task is None:
+        if not self.com.tasks:
             raise ValueError("this rollout has no ComTask")
         t = np.ascontiguousarray(target, dtype=np.float64)
         if t.shape not in ((3,), (self.B, 3)):
             raise ValueError(f"the centre-of-mass target must have shape (3,) or {(self.B, 3)}, got {t.shape}")
-        self.com_batched = t.ndim == 2
-        self.api.put(self.d_com_target, t)
+        self.com.batched = t.ndim == 2
+        self.api.put(self.com.d_target, t)
 
-    def _com_rows(self) -> None:
-        """The ComTask rows (and the centres themselves) of the configurations in ``d_q``, behind the frame rows."""
-        self.api.com_task(self.dmodel, self.dcom, self.B, self.d_q, self.d_com_target, self.com_batched, self.d_e, self.K,
-                          self.d_J, self.Kd * self.nv, 6 * len(self.frames), self.d_com)
+    def _rows(self) -> None:
+        """The rows of the groups of the configurations in ``d_q`` behind the frame rows (com -> manipulability -> wheels), then the barrier rows
+        into the dense rows of the solve: position and spherical rows on the frame slots of the device model, then the sphere-pair rows."""
+        self.layout.launch_all(self.api, self.B, self.d_q, self.d_e, self.K, self.d_J, self.Kd * self.nv)
+        if self.d_Gd is not None:
+            self.bars.launch(self.api, self.B, self.d_q, self.dt, self.d_Gd, self.md * self.nv, self.d_hd, self.md)
 
-    def _manip_rows(self, m_out: bool = False) -> None:
-        """The ManipulabilityTask rows of the configurations in ``d_q``, behind the frame and centre-of-mass rows."""
-        row0 = 6 * len(self.frames) + self.n_com
-        for i, t in enumerate(self.manip_tasks):
-            self.api.manipulability_task(self.mmodel, self.B, self.d_q, i, int(t.reference_frame), t.row_mask, float(t.manipulability_rate),
-                                         self.d_e, self.K, self.d_J, self.Kd * self.nv, row0 + i,
-                                         self.d_manip + 8 * self.B * i if m_out else None)
-
-    def _barrier_rows(self) -> None:
-        """The barrier rows of the configurations in ``d_q`` into the dense rows of the solve (``pinkhip_barrier_rows_device``):
-        position and spherical rows on the frame slots of the device model, then the sphere-pair rows."""
-        self.api.barrier_rows(self.dmodel, self.B, self.d_q, self.dt, self._bar_rows, self._pairs, self.d_Gd, self.md * self.nv,
-                              self.d_hd, self.md, 0)
-
-    def _wheel_rows(self, heights: bool = False) -> None:
-        """The RollingTask / OmniwheelTask rows of the configurations in ``d_q``, behind the frame, centre-of-mass and
-        manipulability rows: one launch for all wheels."""
-        n = len(self.wheel_tasks)
-        self.api.rolling_tasks(self.rmodel, self.B, self.d_q, list(range(n)), self.wheel_kinds, self.wheel_radii, self.d_e, self.K,
-                               self.d_J, self.Kd * self.nv, 6 * len(self.frames) + self.n_com + self.n_manip,
-                               self.d_heights if heights else None)
+    def _group_output(self, g, what: str, shape: tuple) -> np.ndarray:
+        """What the kernel of group ``g`` writes beside its rows, at the current configurations."""
+        if not g.tasks:
+            raise ValueError(f"this rollout has no {what}")
+        self.flush()
+        g.launch(self.api, self.B, self.d_q, self.d_e, self.K, self.d_J, self.Kd * self.nv, g.row0, g.out)  # (the rows it writes are formed anew by every step)
+        self.api.sync()
+        out = np.zeros(shape)
+        self.api.get(out, g.out)
+        return out
 
     def wheel_heights(self) -> np.ndarray:
-        """``[B, n_wheels]``: heights of the hubs over their floors' planes at the current configurations, computed on the
-        device."""
-        if not self.wheel_tasks:
-            raise ValueError("this rollout has no RollingTask / OmniwheelTask")
-        self.flush()
-        self._wheel_rows(heights=True)  # (the rows it writes are formed anew by every step)
-        self.api.sync()
-        z = np.zeros((self.B, len(self.wheel_tasks)))
-        self.api.get(z, self.d_heights)
-        return z
+        """``[B, n_wheels]``: heights of the hubs over their floors' planes at the current configurations, computed on the device."""
+        return self._group_output(self.wheels, "RollingTask / OmniwheelTask", (self.B, len(self.wheels.tasks)))
 
     def manipulability(self) -> np.ndarray:
         """``[n_tasks, B]``: manipulability indices of the current configurations, computed on the device."""
-        if not self.manip_tasks:
-            raise ValueError("this rollout has no ManipulabilityTask")
-        self.flush()
-        self._manip_rows(m_out=True)  # (the rows it writes are formed anew by every step)
-        self.api.sync()
-        m = np.zeros((self.n_manip, self.B))
-        self.api.get(m, self.d_manip)
-        return m
+        return self._group_output(self.manip, "ManipulabilityTask", (len(self.manip.tasks), self.B))
 
     def center_of_mass(self) -> np.ndarray:
         """``[B, 3]``: centres of mass of the current configurations, computed on the device."""
-        if self.com_task is None:
-            raise ValueError("this rollout has no ComTask")
-        self.flush()
-        self._com_rows()  # (the rows it writes are formed anew by every step)
-        self.api.sync()
-        c = np.zeros((self.B, 3))
-        self.api.get(c, self.d_com)
-        return c
+        return self._group_output(self.com, "ComTask", (self.B, 3))
 
     def step(self, integrate: bool = True) -> None:
         """Enqueue one IK step for every robot (asynchronous).  ``integrate=False`` only solves (dq, status and
@@ -841,14 +734,7 @@ class DeviceRollout:
             st.lb, st.ub, st.e_off = self.d_lb, self.d_ub, self.Kd
             st.root_box = self.d_lim[0] if self.d_lim else None
             a.step_kernel(self.dmodel, B, st)
-            if self.com_task is not None:  # (the step kernel has advanced q already)
-                self._com_rows()
-            if self.manip_tasks:
-                self._manip_rows()
-            if self.wheel_tasks:
-                self._wheel_rows()
-            if self.d_Gd is not None:
-                self._barrier_rows()
+            self._rows()  # (the step kernel has advanced q already)
             a.solve_raw(self.desc, self.problem, self.result)
             self._pending = bool(integrate)
         else:  # one launch for FK, one per FrameTask, limits + posture, solve, integrate
@@ -859,14 +745,7 @@ class DeviceRollout:
                                      self.d_J + 8 * 6 * nv * t, self.Kd * nv)
             a.limits_posture(self.dmodel, B, self.dt, self.config_limit_gain, self.d_q, self.d_qt, self.qt_batched, self.d_lb, self.d_ub,
                              self.d_e if self.n_post else None, self.K, self.Kd)
-            if self.com_task is not None:
-                self._com_rows()
-            if self.manip_tasks:
-                self._manip_rows()
-            if self.wheel_tasks:
-                self._wheel_rows()
-            if self.d_Gd is not None:
-                self._barrier_rows()
+            self._rows()
             a.solve_raw(self.desc, self.problem, self.result)
             if integrate:
                 a.integrate_checked(self.dmodel, B, self.d_q, self.d_dq, self.d_status, self.d_fail, self.steps_done)
@@ -1163,23 +1042,6 @@ class DeviceRollout:
                     getattr(self, "d_pairs", [])):
             self.api.release(ptr)
         self.d_bar, self.d_lim, self.d_extra, self.d_cons, self.d_pairs = [], [], [], [], []
-        if getattr(self, "d_acc", None) is not None:
-            self.api.release(self.d_acc)
-            self.d_acc = None
-        if getattr(self, "d_active", None) is not None:
-            self.api.release(self.d_active)
-            self.d_active = None
-        if getattr(self, "mmodel", None) is not None:
-            self.api.model_destroy(self.mmodel)
-            self.mmodel = None
-        if getattr(self, "rmodel", None) is not None:
-            self.api.model_destroy(self.rmodel)
-            self.rmodel = None
-        for name in ("d_com", "d_com_target", "d_manip", "d_heights", "d_Gd", "d_hd"):
-            if getattr(self, name, None) is not None:
-                self.api.release(getattr(self, name))
-                setattr(self, name, None)
-        if getattr(self, "dcom", None) is not None:
-            self.api.com_destroy(self.dcom)
-            self.dcom = None
+        if getattr(self, "layout", None) is not None:
+            self.layout.free()
         self.api.model_destroy(self.dmodel)

@@ -504,14 +504,11 @@ def _device_kinematics_plan(configurations, tasks, limits, barriers, constraints
     if why is not None:
         return _declined(why)
     flat = [t for entry in (tasks or ()) for t in (entry if isinstance(entry, (list, tuple)) else (entry,))]
-    from .tasks.manipulability_task import ManipulabilityTask
+    from .row_groups import ManipulabilityGroup, WheelGroup
 
-    if any(isinstance(t, ManipulabilityTask) for t in flat):
-        return _declined("ManipulabilityTask: the whole-step kernel does not form its row (the hybrid route does)")
-    from .tasks.rolling_task import RollingTask
-
-    if any(isinstance(t, RollingTask) for t in flat):
-        return _declined("RollingTask / OmniwheelTask: the whole-step kernel does not form wheel-contact rows (the hybrid route does)")
+    for kind in (ManipulabilityGroup, WheelGroup):
+        if any(isinstance(t, kind.types) for t in flat):
+            return _declined(f"{kind.needs[2:]}: the whole-step kernel does not form {kind.rows} (the hybrid route does)")
     plan = _device_kinematics_plan_tasks(configurations, tasks)
     if plan is None:
         return _declined("a task the whole-step kernel does not form (FrameTask / RelativeFrameTask, one PostureTask, table-formed tasks shared by the batch)")
@@ -1102,14 +1099,8 @@ def _solve_hybrid(configurations, tasks, dt, damping, limits, barriers, constrai
         make = lambda: BatchKinematics(model, q)  # noqa: E731
     slots = _task_slots(tasks, B)
     cslots = _task_slots(constraints, B) if constraints else []
-    frame_slots = hybrid.plan(model, slots, cslots)
+    frame_slots = hybrid.plan(model, slots, cslots, api)  # (None also for a solver without the kernel of a row group of the stack)
     if frame_slots is None:
-        return None
-    if hybrid.com_slot(slots) is not None and not hasattr(api, "com_task"):  # (a solver without the centre-of-mass kernel)
-        return None
-    if hybrid.manipulability_slots(slots) and not hasattr(api, "manipulability_task"):  # (a solver without the manipulability kernel)
-        return None
-    if hybrid.rolling_slots(slots) and not hasattr(api, "rolling_tasks"):  # (a solver without the wheel-contact kernel)
         return None
     if limits is None:  # model defaults, pink/solve_ik.py:94-105
         model.ensure_limits()
